@@ -1,6 +1,6 @@
 """bench.py -- utterances/sec (fwd + loss + bwd) of the MM-DFN hot path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgK] [--ragged]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgK] [--ragged] [--dump-outputs DIR] [--full]
 
 Workload: BASELINE configs[1] (cfg2: 16 dialogues of 110 utterances) on one GPU; with --gpus N > 1 BASELINE configs[3]
 (cfg4: 32 dialogues per GPU = 256 at 8 GPUs), weak scaling.  --ragged at N > 1 draws ONE global batch of 32 N dialogues
@@ -16,13 +16,23 @@ One "step" = zero_grad -> DialogueGNNModel forward -> FocalLoss -> backward (+ t
 when N > 1) on one synthetic IEMOCAP-shaped batch already resident in HBM.  Weak scaling: every rank processes its own
 batch of the configured size (dialogues are independent; the only collective is the flat-bucket gradient all-reduce).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the outputs if asked, print
+ONE JSON line (rank 0) with the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+milliseconds of one timed step, ...).  --dump-outputs DIR writes what the last timed step handed its caller (loss,
+log-probabilities, every parameter's gradient) as float32 DIR/<name>.npy; inputs, weights and the dropout stream are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures, each in runs of its own after the headline (the --no-* options
+below drop single legs of it):
+  "with_fused_adam_step": the same step followed by the fused Adam update
+  "self_check":    --gpus N > 1: per-rank compute-only times against the ring all-reduce model
   "roofline":      live HIP-event timing of the north-star kernel (K6 scatter-propagate) vs the HBM roofline at the
                    bench workload; "roofline_cfg5*": the same kernel family at BASELINE config 5, where one launch moves
                    282 MB (the >= 40 % target is a cfg5 property), buffers rotated so nothing is served by the MALL
   "dominant":      what actually bounds the step at this workload (per-kernel shares from the committed rocprof stats)
   "cpu_baseline":  the CPU oracle (port of the reference's op structure) and, next to it, the vectorised CPU
                    restatement, timed on this host on the same batch, N=1 only.
+  "other_workloads": cfg2 ragged, cfg2_refdims, cfg3, cfg4, cfg5 and the streamed pass loop, N=1 only.
 """
 import argparse
 import json
@@ -35,6 +45,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -47,6 +58,11 @@ def parse():
                          "GPU, 256 at 8 GPUs) at --gpus N > 1")
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--dropout", type=float, default=0.5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the fused-Adam leg, the K6 roofline legs, the step floor, the other "
+                         "workloads, the CPU baseline and (N > 1) the self-check; a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the loss, log-probabilities and parameter gradients of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--two-part-bucket", action="store_true",
                     help="data parallel: reduce the graph / head half of the gradient bucket while the encoders' backward is "
@@ -524,10 +540,29 @@ def cpu_baseline(cfg, batch, state, threads, dropout, budget_s):
     return port
 
 
+def dump_outputs(path, loss, logp, model):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the log-probabilities (N, C) and every
+    parameter's gradient -- as float32 ``path``/<name>.npy.  Should they exceed DUMP_LIMIT_BYTES, every array larger than
+    its share is replaced by a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    arrays = {"loss": loss, "log_prob": logp}
+    arrays.update(("grad." + n, p.grad) for n, p in model.named_parameters() if p.grad is not None)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // (4 * len(arrays))
+    sample = sum(v.nbytes for v in arrays.values()) > DUMP_LIMIT_BYTES
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        if sample and v.size > share:
+            v = v.reshape(-1)[np.sort(np.random.RandomState(0).choice(v.size, share, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     a = parse()
     if a.config is None:
         a.config = "cfg2" if (a.gpus == 1 and not a.predict_scaling) else "cfg4"
+    if a.dump_outputs and (a.predict_scaling or a.only_roofline):
+        raise SystemExit("--dump-outputs writes the headline step's outputs: not with --predict-scaling / --only-roofline")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
     # stdout carries ONE JSON line and nothing else: libraries that print to the C-level stdout (RCCL's version banner
@@ -547,6 +582,7 @@ def main():
         raise SystemExit("--gpus %d but only %d visible devices" % (world, torch.cuda.device_count()))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    torch.manual_seed(2021)   # the dropout stream (torch's generator seeds the package's flag draws): same outputs run to run
     from mm_dfn_amd import FocalLoss, synthetic, train, ops, distributed
     if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)   # eager + captured steps share parameters
@@ -594,9 +630,12 @@ def main():
     total_utt = distributed.all_reduce_scalar(n_utt) if use_dp else n_utt
 
     scale = (n_utt / total_utt) if dp is not None else 1.0   # local mean -> this rank's share of the GLOBAL mean
+    last = {} if (a.dump_outputs and rank == 0) else None    # --dump-outputs: the step's log-probabilities stay referenced
 
     def fwd_bwd():
         logp = model(batch["textf"], batch["qmask"], batch["umask"], lengths, batch["acouf"], batch["visuf"])[0]
+        if last is not None:
+            last["logp"] = logp
         loss = loss_f(logp, label)
         if dp is not None:
             loss = loss * scale        # the summed bucket is then the gradient of the mean over ALL ranks' utterances
@@ -664,11 +703,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        loss = step()
     torch.cuda.synchronize()
     if use_dp:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    if last is not None:
+        dump_outputs(a.dump_outputs, loss, last["logp"], model)
     if use_dp:
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, (dt / a.steps * 1e3, n_utt))
@@ -680,7 +721,7 @@ def main():
     # times ITS OWN shard without the collective, rank 0 adds the modelled ring all-reduce of --predict-scaling and prints
     # the prediction next to what was measured, plus the per-rank times (imbalance) and whether the collective was captured.
     self_check = None
-    if use_dp and world > 1:
+    if a.full and use_dp and world > 1:
         try:
             from mm_dfn_amd.graphs import CapturedStep
 
@@ -710,7 +751,7 @@ def main():
     # ---- the same step followed by the fused Adam update (one extra launch), reported next to the headline.
     # Parameters and gradients are flat buffers here, so the step is re-captured against the flat storage.
     adam_ms = None
-    if not use_dp and not a.no_graph and launch_mode != "eager":
+    if a.full and not use_dp and not a.no_graph and launch_mode != "eager":
         try:
             from mm_dfn_amd.graphs import CapturedStep
             from mm_dfn_amd.optim import FlatAdam
@@ -741,9 +782,11 @@ def main():
                                       cfg["B"], "ragged<=%d" % cfg["L"] if a.ragged else cfg["L"], cfg["D_t"],
                                       cfg["D_a"], cfg["D_v"], cfg["nlayers"], cfg["P"], a.dropout),
                        "utterances_per_gpu": n_utt, "parallelism": "dp%d" % world},
-            "with_fused_adam_step": None if adam_ms is None else {"ms_per_step": adam_ms,
-                                                                   "value": total_utt / (adam_ms * 1e-3)},
+            "full": a.full,
         }
+        if a.full:
+            out["with_fused_adam_step"] = None if adam_ms is None else {"ms_per_step": adam_ms,
+                                                                        "value": total_utt / (adam_ms * 1e-3)}
         if use_dp:
             out["per_rank"] = {"ms_per_step": [x[0] for x in per_rank], "utterances": [x[1] for x in per_rank]}
             if shard_info is not None:
@@ -752,16 +795,17 @@ def main():
                 out["self_check"] = self_check
         if dp is not None and dp.flat is not None:
             out["gradient_bucket"] = {"floats": dp.flat.numel(), "bytes": dp.flat.numel() * 4, "backend": a.backend}
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             roofline_legs(out, a, dev, n_utt, lengths)
-        out["dominant"] = (profile_json("r06_step_breakdown_%s.json" % a.config) or profile_json("r05_step_breakdown_%s.json" % a.config)
-                           or profile_json("r04_step_breakdown_%s.json" % a.config))
-        try:
-            out["dominant"] = attach_step_floor(out["dominant"], a.config, [int(x) for x in lengths],
-                                                1.45 if a.no_floor else dependent_launch_us())
-        except Exception as exc:
-            print("[bench] step floor not attached: %s: %s" % (type(exc).__name__, exc), file=sys.stderr)
-        if world == 1 and not a.no_extra and not use_dp:
+        if a.full:
+            out["dominant"] = (profile_json("r06_step_breakdown_%s.json" % a.config) or profile_json("r05_step_breakdown_%s.json" % a.config)
+                               or profile_json("r04_step_breakdown_%s.json" % a.config))
+            try:
+                out["dominant"] = attach_step_floor(out["dominant"], a.config, [int(x) for x in lengths],
+                                                    1.45 if a.no_floor else dependent_launch_us())
+            except Exception as exc:
+                print("[bench] step floor not attached: %s: %s" % (type(exc).__name__, exc), file=sys.stderr)
+        if a.full and world == 1 and not a.no_extra and not use_dp:
             out["other_workloads"] = []
             legs = [lambda c=c, r=r: quick_leg(c, r, a.dropout) for c, r in
                     (("cfg2", True), ("cfg2_refdims", False), ("cfg3", True), ("cfg4", False), ("cfg4", True))]
@@ -773,7 +817,7 @@ def main():
                 except Exception as exc:
                     print("[bench] extra workload skipped: %s: %s" % (type(exc).__name__, exc), file=sys.stderr)
                 torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline and not use_dp:
+        if a.full and world == 1 and not a.no_cpu_baseline and not use_dp:
             out["cpu_baseline"] = cpu_baseline(cfg, batch, model.state_dict(), a.cpu_threads, a.dropout, a.cpu_budget)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if use_dp:

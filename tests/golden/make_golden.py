@@ -348,11 +348,76 @@ def export_state_keys():
     print("keys", len(keys))
 
 
+ORACLE_VS_REFERENCE_CASES = [(2, 2, [18, 7, 11]), (9, 3, [12, 1, 5, 9])]    # (P, nlayers, lengths): D_t/D_a/D_v = 100/48/64
+
+
+def export_oracle_vs_reference():
+    """tests/test_oracle_vs_reference.py: eval log-probabilities of the reference model (weights seeded from its own
+    state_dict, seed 7; batch seed 8) and its create_big_adj on RandomState(3) features."""
+    out = {}
+    for P, nl, lengths in ORACLE_VS_REFERENCE_CASES:
+        cfg = dict(B=len(lengths), L=max(lengths), P=P, C=6, nlayers=nl, D_t=100, D_a=48, D_v=64)
+        ref = ref_shim.build_reference_model(100, 48, 64, P, 6, nl).eval()
+        ref.load_state_dict(synthetic.seeded_state_dict(ref.state_dict(), 7))
+        b = synthetic.make_batch(8, lengths=lengths, **cfg)
+        with torch.no_grad():
+            out["logp_P%d_nl%d" % (P, nl)] = ref(b["textf"], b["qmask"], b["umask"], b["lengths"], b["acouf"],
+                                                 b["visuf"])[0].numpy()
+    ref = ref_shim.build_reference_model(100, 48, 64, 2, 6, 2)
+    rs = np.random.RandomState(3)
+    lengths = [14, 6, 1]
+    feats = [torch.from_numpy(rs.randn(sum(lengths), 200).astype(np.float32)) for _ in range(3)]
+    with torch.no_grad():
+        out["adj_avl"] = ref.graph_model.create_big_adj(feats[0], feats[1], feats[2], lengths, ['a', 'v', 'l']).numpy()
+        out["adj_av"] = ref.graph_model.create_big_adj(feats[0], feats[1], [], lengths, ['a', 'v']).numpy()
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_reference.npz"), **out)
+    print("oracle vs reference ok")
+
+
+def export_dataloader():
+    """tests/test_data_and_fit.py: what the reference's IEMOCAPDataset / MELDDataset return for a small synthetic feature
+    file (mm_dfn_amd.data.write_synthetic_pickle, seed 3): every item, the collated batch, MELD's return_labels()."""
+    import tempfile
+    from mm_dfn_amd import data as D
+    ref_shim.install()
+    import dataloader as R  # the reference's module
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name in ("IEMOCAP", "MELD"):
+            p = D.write_synthetic_pickle(os.path.join(tmp, name + ".pkl"), dataset=name, n_train=7, n_test=3,
+                                         n_speakers=2 if name == "IEMOCAP" else 9, n_classes=6 if name == "IEMOCAP" else 7,
+                                         D_t=20, D_a=12, D_v=16, seed=3)
+            for train in (True, False):
+                ref = getattr(R, name + "Dataset")(p, train)
+                pre = "%s_%s_" % (name, "train" if train else "test")
+                items = [ref[i] for i in range(len(ref))]
+                out[pre + "len"] = np.array(len(ref))
+                for i, it in enumerate(items):
+                    for j in range(6):
+                        out[pre + "item%d_%d" % (i, j)] = it[j].numpy()
+                    out[pre + "item%d_vid" % i] = np.array(it[6])
+                batch = ref.collate_fn(items)
+                out[pre + "collate_len"] = np.array(len(batch))
+                for j in range(6):
+                    out[pre + "collate_%d" % j] = batch[j].numpy()
+                out[pre + "collate_vids"] = np.array(batch[6])
+                if name == "MELD":
+                    out[pre + "return_labels"] = np.array(ref.return_labels(), dtype=np.int64)
+    np.savez_compressed(os.path.join(HERE, "dataloader.npz"), **out)
+    print("dataloader ok")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     if "--variants-only" in sys.argv:          # (round 5: the bimodal / av_using_lstm fixtures, without touching the others)
         export_variants()
         sys.exit(0)
+    if "--live-tests-only" in sys.argv:        # the fixtures of the tests that once imported the reference live
+        export_oracle_vs_reference()
+        export_dataloader()
+        sys.exit(0)
+    export_oracle_vs_reference()
+    export_dataloader()
     export_variants()
     export_state_keys()
     export_fusion_modules()

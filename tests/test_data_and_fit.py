@@ -1,9 +1,8 @@
-"""Host logic next to the hot path: the pickle -> Dataset -> collate contract against the
-reference's own dataloader classes (when /root/reference is present), the bucketing sampler, and the dual-patience
-epoch loop against a literal restatement of run_train_erc.py:609-639."""
+"""Host logic next to the hot path: the pickle -> Dataset -> collate contract against what the
+reference's own dataloader classes return (tests/golden/dataloader.npz, exported by tests/golden/make_golden.py), the
+bucketing sampler, and the dual-patience epoch loop against a literal restatement of run_train_erc.py:609-639."""
 import os
 import pickle
-import sys
 
 import numpy as np
 import pytest
@@ -13,36 +12,32 @@ from mm_dfn_amd import data as D
 from mm_dfn_amd import train as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
-import ref_shim  # noqa: E402
 
 
 @pytest.mark.parametrize("name", ["IEMOCAP", "MELD"])
 def test_dataset_items_and_collate_match_reference(tmp_path, name):
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
-    ref_shim.install()
-    import dataloader as R  # the reference's module
+    ref = np.load(os.path.join(HERE, "golden", "dataloader.npz"))
     p = str(tmp_path / "f.pkl")
     D.write_synthetic_pickle(p, dataset=name, n_train=7, n_test=3, n_speakers=2 if name == "IEMOCAP" else 9,
                              n_classes=6 if name == "IEMOCAP" else 7, D_t=20, D_a=12, D_v=16, seed=3)
     for train in (True, False):
+        pre = "%s_%s_" % (name, "train" if train else "test")
         ours = getattr(D, name + "Dataset")(p, train)
-        ref = getattr(R, name + "Dataset")(p, train)
-        assert len(ours) == len(ref)
+        assert len(ours) == int(ref[pre + "len"])
         items_o = [ours[i] for i in range(len(ours))]
-        items_r = [ref[i] for i in range(len(ref))]
-        for a, b in zip(items_o, items_r):
-            for x, y in zip(a[:6], b[:6]):
+        for i, a in enumerate(items_o):
+            for j, x in enumerate(a[:6]):
+                y = torch.from_numpy(ref[pre + "item%d_%d" % (i, j)])
                 assert x.dtype == y.dtype and torch.equal(x, y)
-            assert a[6] == b[6]
-        bo, br = ours.collate_fn(items_o), ref.collate_fn(items_r)
-        assert len(bo) == len(br) == 7
-        for x, y in zip(bo[:6], br[:6]):
-            assert x.shape == y.shape and torch.equal(x, y)
-        assert bo[6] == br[6]
-    if name == "MELD":
-        assert ours.return_labels() == ref.return_labels()
+            assert a[6] == str(ref[pre + "item%d_vid" % i])
+        bo = ours.collate_fn(items_o)
+        assert len(bo) == int(ref[pre + "collate_len"]) == 7
+        for j, x in enumerate(bo[:6]):
+            y = torch.from_numpy(ref[pre + "collate_%d" % j])
+            assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y)
+        assert bo[6] == [str(v) for v in ref[pre + "collate_vids"]]
+        if name == "MELD":
+            assert ours.return_labels() == [int(v) for v in ref[pre + "return_labels"]]
 
 
 def test_batch_layout_without_reference(tmp_path):

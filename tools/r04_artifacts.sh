@@ -3,7 +3,7 @@
 # steps and of the K6 roofline legs, step breakdowns, PMC traffic of the roofline legs.  Outputs under gpurun_out/r04/ (copied to
 # profiles/ by hand).    usage: tools/r04_artifacts.sh <commit>
 out=gpurun_out/r04; mkdir -p $out
-python bench.py > $out/bench_cfg2.json 2> $out/bench_cfg2.err
+python bench.py --full > $out/bench_cfg2.json 2> $out/bench_cfg2.err
 TAILN=2 TOPN=0 tools/prof_stats.sh r04_bench_cfg2 python bench.py --no-extra --no-roofline --no-cpu-baseline
 TAILN=2 TOPN=0 tools/prof_stats.sh r04_bench_cfg3 python bench.py --config cfg3 --ragged --no-extra --no-roofline --no-cpu-baseline --steps 30 --warmup 10
 TAILN=2 TOPN=0 tools/prof_stats.sh r04_bench_cfg4 python bench.py --config cfg4 --no-extra --no-roofline --no-cpu-baseline --steps 30 --warmup 10
