@@ -10,7 +10,8 @@
  *
  * Conventions (all entry points):
  *   - every pointer is a DEVICE pointer owned by the caller (the PyTorch
- *     caching allocator); kernels never allocate or free;
+ *     caching allocator); kernels never allocate or free.  The one exception
+ *     is `riders`, a HOST rider context (see mmdfn_riders_bytes);
  *   - fp32 row-major contiguous data, int32 / int64 index arrays;
  *   - asynchronous enqueue on `stream` (a hipStream_t passed as void*), no
  *     internal synchronisation, no global state, re-entrant;
@@ -39,7 +40,15 @@
 extern "C" {
 #endif
 
-/* Library / device sanity: returns the ABI version (currently 17: 16 + the GRU backward launch's weight-gradient riders mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_gru_seq_bwd_idle_cus, mmdfn_gru_seq_bwd_step_ns, and the dropout-flag draw as a rider of the GRU forward launch mmdfn_keep_flags_{stage,flush}, mmdfn_gru_seq_fwd_takes_flags; 16 = 15 + mmdfn_linear_planes_group, mmdfn_party_gather_bwd_colsum, mmdfn_party_combine_bwd_dst, mmdfn_prop_layer_fwd; 15 = 14 + mmdfn_weight_planes_workspace, mmdfn_cut_weight_planes, mmdfn_linear_planes; 14 = 13 + mmdfn_lstm_gate_{planes_workspace,cut_weights,fwd_pre,takes_planes}; 13 = 12 + mmdfn_gemm_tn_batch_ext, mmdfn_head_bwd_partial / _groups, mmdfn_colsum_partial; 12 = 11 + the segmented GRU recurrence mmdfn_gru_seq_{fwd,bwd}_seg, mmdfn_gru_tab_reduce, the strided forms mmdfn_lstm_gate_fwd_ld, mmdfn_gcnii_layer_bwd_ld, mmdfn_focal_loss_{fwd,bwd}_ignore and mmdfn_focal_loss_fwd_grad). */
+/* Rider context: HOST memory of mmdfn_riders_bytes() bytes, owned by the caller; all-zero bytes = empty.  Work staged in it
+ * (mmdfn_wgrad_riders_stage, mmdfn_keep_flags_stage) is taken only by a launch given the same context; the library never
+ * allocates, frees or keeps a pointer to it beyond a call.  NULL wherever a `riders` argument is taken = no riders: nothing is
+ * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
+int64_t mmdfn_riders_bytes(void);
+
+/* Library / device sanity: returns the ABI version (currently 18: 17 with the rider hand-off made explicit -- the rider context
+ * `riders` (mmdfn_riders_bytes) is an argument of mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_keep_flags_{stage,flush},
+ * mmdfn_gru_seq_{fwd,bwd} and mmdfn_gemm_tn_batch / _ext; 17 = 16 + the GRU backward launch's weight-gradient riders mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_gru_seq_bwd_idle_cus, mmdfn_gru_seq_bwd_step_ns, and the dropout-flag draw as a rider of the GRU forward launch mmdfn_keep_flags_{stage,flush}, mmdfn_gru_seq_fwd_takes_flags; 16 = 15 + mmdfn_linear_planes_group, mmdfn_party_gather_bwd_colsum, mmdfn_party_combine_bwd_dst, mmdfn_prop_layer_fwd; 15 = 14 + mmdfn_weight_planes_workspace, mmdfn_cut_weight_planes, mmdfn_linear_planes; 14 = 13 + mmdfn_lstm_gate_{planes_workspace,cut_weights,fwd_pre,takes_planes}; 13 = 12 + mmdfn_gemm_tn_batch_ext, mmdfn_head_bwd_partial / _groups, mmdfn_colsum_partial; 12 = 11 + the segmented GRU recurrence mmdfn_gru_seq_{fwd,bwd}_seg, mmdfn_gru_tab_reduce, the strided forms mmdfn_lstm_gate_fwd_ld, mmdfn_gcnii_layer_bwd_ld, mmdfn_focal_loss_{fwd,bwd}_ignore and mmdfn_focal_loss_fwd_grad). */
 int mmdfn_abi_version(void);
 
 /* ---------------------------------------------------------------------------
@@ -114,7 +123,7 @@ int mmdfn_adj_build_bwd(const float* dtiles, const float* dcross,
  * ------------------------------------------------------------------------- */
 int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const float* const* w_hh,
                       const float* const* b_hh, float* const* y, float* const* gates,
-                      const int* rows, const int* T, int H, void* stream);
+                      const int* rows, const int* T, int H, void* riders, void* stream);
 
 /* Backward through time of the same recurrence: given dy[g] (T, rows, 2H) writes
  *   dgi[g], dgh[g] : (T, rows, 2, 3H)  gradients of the input-side / hidden-side gate
@@ -123,7 +132,7 @@ int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const float* const* w
 int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const float* const* y,
                       const float* const* gates, const float* const* w_hh,
                       float* const* dgi, float* const* dgh,
-                      const int* rows, const int* T, int H, void* stream);
+                      const int* rows, const int* T, int H, void* riders, void* stream);
 
 /* Valid-length ("segmented") form of the same recurrence for the speaker-party batch (model.py:1076-1087: per dialogue b and
  * speaker p the reference fills rows [:k_bp] of a zero (L, H) buffer, runs the party GRU over all L steps and scatters rows
@@ -221,15 +230,16 @@ int mmdfn_party_gather_bwd_colsum(int Mn, const float* dS, const int32_t* rank, 
  * state[0] (seed) at counter state[1] + i / 8 (16 random bits per flag: the rate is exact to 2^-16).  `state`: three 64-bit words
  * in DEVICE memory (seed, offset, 0); the launch adds ceil(n / 8) rounded up to a multiple of 64 to the offset itself, so replays of a captured graph draw fresh flags. */
 int mmdfn_keep_flags(float* out, int64_t n, float keep, void* state, void* stream);
-/* ABI 17: the same draw as a RIDER of the first GRU layer's forward recurrence launch.  mmdfn_keep_flags_stage takes the arguments
- * of mmdfn_keep_flags and does not launch (a second staged draw is launched at once); the next mmdfn_gru_seq_fwd launch of the kind
- * mmdfn_gru_seq_fwd_takes_flags answers 1 for (one sequence per workgroup, fewer workgroups than CUs) runs the draw as extra
- * workgroups on the CUs the recurrence leaves idle -- the same flags bit for bit (which counter yields which flag depends on
- * neither the grid nor the block size); mmdfn_keep_flags_flush launches a draw that is still staged.  The flags must not be read
+/* The same draw as a RIDER of the first GRU layer's forward recurrence launch.  mmdfn_keep_flags_stage takes the arguments of
+ * mmdfn_keep_flags and stages the draw in `riders` instead of launching it (a second staged draw, or riders = NULL: launched at
+ * once); a mmdfn_gru_seq_fwd launch given the same context, of the kind mmdfn_gru_seq_fwd_takes_flags answers 1 for (fewer
+ * workgroups than CUs), runs the draw as extra workgroups on the CUs the recurrence leaves idle -- the same flags bit for bit
+ * (which counter yields which flag depends on neither the grid nor the block size); mmdfn_keep_flags_flush launches a draw that
+ * is still staged.  The flags must not be read
  * before the launch that carries them (their first consumer in the reference is the dropout behind that GRU layer,
  * model.py:866). */
-int mmdfn_keep_flags_stage(float* out, int64_t n, float keep, void* state, void* stream);
-int mmdfn_keep_flags_flush(void* stream);
+int mmdfn_keep_flags_stage(float* out, int64_t n, float keep, void* state, void* riders, void* stream);
+int mmdfn_keep_flags_flush(void* riders, void* stream);
 int mmdfn_gru_seq_fwd_takes_flags(int ngroups, const int* rows);
 int64_t mmdfn_colsum_workspace(int H);
 int mmdfn_colsum(const float* A, int64_t R, int H, int lda, float* out, float* workspace, void* stream);
@@ -478,7 +488,7 @@ int64_t mmdfn_gemm_tn_batch_workspace(int nseg, const int* R, const int* out, in
 int mmdfn_gemm_tn_batch(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
                         const int* ldb, const int* bshift, const int* out, int nout, float* const* C,
                         float* const* colsum, float* const* colsum2, const int* M, const int* N, const int* ldc,
-                        const int* accumulate, float* workspace, void* stream);
+                        const int* accumulate, float* workspace, void* riders, void* stream);
 /* The same batch whose reduction launch ALSO sums `next` slab stacks written by other kernels (ABI 13): stack e holds
  * ext_splits[e] slabs of ext_M[e] x ext_N[e] floats (ext_part[e], summed into ext_C[e] of row stride ext_ldc[e]; ext_N[e] = 0:
  * none) and / or of ext_M[e] floats (ext_colpart[e], summed into ext_colsum[e]; NULL: none), in slab order (bit-reproducible);
@@ -491,35 +501,37 @@ int mmdfn_gemm_tn_batch_ext(int nseg, const float* const* A, const float* const*
                             const int* accumulate, float* workspace, int next, const float* const* ext_part,
                             const float* const* ext_colpart, float* const* ext_C, float* const* ext_colsum, const int* ext_M,
                             const int* ext_N, const int* ext_ldc, const int* ext_splits, const int* ext_accumulate,
-                            void* stream);
+                            void* riders, void* stream);
 
-/* Weight-gradient RIDERS of the GRU backward recurrence launch (ABI 17).  The backward recurrence of nn.GRU (reference
- * model.py:866-868: autograd of the context / party GRUs) keeps one CU per sequence busy for ~T x 0.75 us and leaves the other
+/* Weight-gradient RIDERS of the GRU backward recurrence launch (ABI 17; the `riders` context: 18).  The backward recurrence of
+ * nn.GRU (reference model.py:866-868: autograd of the context / party GRUs) keeps one CU per sequence busy for ~T x 0.75 us and leaves the other
  * CUs idle (IEMOCAP batch of 16: 160 of 256).  mmdfn_wgrad_riders_stage takes the arguments of mmdfn_gemm_tn_batch, plans the
  * batch and allocates its slabs exactly as that call would, but -- when the batch runs on the bf16-piece form, has at most 16
- * segments and nothing is staged yet -- does NOT launch it: the next mmdfn_gru_seq_bwd call on a one-sequence-per-workgroup
- * launch runs the batch's tiles as extra workgroups of the recurrence launch (never on a CU that holds a recurrence: the
- * launch's LDS request keeps every CU to one workgroup); the slab reduction follows later (mmdfn_wgrad_riders_drain).  A batch that cannot ride is
- * launched by the stage call itself.  mmdfn_wgrad_riders_staged: 1 while a batch waits; mmdfn_wgrad_riders_flush launches a
- * waiting batch the ordinary way (call it where no GRU backward launch will follow).  The operands and the workspace must stay
- * valid until the launch that consumes them has been issued on `stream` (the same stream for all three calls).  Results are
- * those of mmdfn_gemm_tn_batch bit for bit (same tiles, same slab order). */
+ * segments and nothing is staged in `riders` yet -- stages it there instead of launching it: a mmdfn_gru_seq_bwd call given the
+ * same context, on a launch with idle CUs (mmdfn_gru_seq_bwd_idle_cus), runs the batch's tiles as extra workgroups of the
+ * recurrence launch (never on a CU that holds a recurrence: the launch's LDS request keeps every CU to one workgroup); the slab
+ * reduction follows later (mmdfn_wgrad_riders_drain).  A batch that cannot ride is launched by the stage call itself.
+ * mmdfn_wgrad_riders_staged: 1 while a batch waits in the context; mmdfn_wgrad_riders_flush launches a waiting batch the
+ * ordinary way (call it where no GRU backward launch will follow).  The operands and the workspace must stay valid until the
+ * launch that consumes them has been issued on `stream` (the same stream for all three calls).  Results are those of
+ * mmdfn_gemm_tn_batch bit for bit (same tiles, same slab order). */
 int mmdfn_wgrad_riders_stage(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
                              const int* ldb, const int* bshift, const int* out, int nout, float* const* C,
                              float* const* colsum, float* const* colsum2, const int* M, const int* N, const int* ldc,
-                             const int* accumulate, float* workspace, void* stream);
-int mmdfn_wgrad_riders_staged(void);
+                             const int* accumulate, float* workspace, void* riders, void* stream);
+int mmdfn_wgrad_riders_staged(void* riders);
 /* CUs the mmdfn_gru_seq_bwd launch of these groups leaves idle if it is of the kind that takes riders, else 0: stage a batch
  * only when this is > 0, and size it for that many CUs over the recurrence's ~0.75 us x T. */
 int mmdfn_gru_seq_bwd_idle_cus(int ngroups, const int* rows);
 int mmdfn_gru_seq_bwd_step_ns(int ngroups, const int* rows);    /* ns per recurrence step of that launch (750 / 2300: the two forms) */
-int mmdfn_wgrad_riders_flush(void* stream);
-/* The slab reduction of a batch that rode (or that mmdfn_wgrad_riders_flush launched) is not a launch of its own either: it joins the reduction launch of the next
- * mmdfn_gemm_tn_batch / _ext call on the stream (unless that call writes one of the same gradients: then it goes first, alone).
- * mmdfn_wgrad_riders_drain(stream, 0) reduces what is still waiting -- call it once at the end of the backward pass, behind the
+int mmdfn_wgrad_riders_flush(void* riders, void* stream);
+/* The slab reduction of a batch that rode (or that mmdfn_wgrad_riders_flush launched) is not a launch of its own either: it waits
+ * in the context and joins the reduction launch of the next mmdfn_gemm_tn_batch / _ext call given that context (unless that call
+ * writes one of the same gradients: then it goes first, alone).
+ * mmdfn_wgrad_riders_drain(riders, stream, 0) reduces what is still waiting -- call it once at the end of the backward pass, behind the
  * last batch; the slabs (the staged batches' workspaces) must stay valid until then.  discard != 0 forgets staged and waiting
  * work instead (after a backward pass that raised). */
-int mmdfn_wgrad_riders_drain(void* stream, int discard);
+int mmdfn_wgrad_riders_drain(void* riders, void* stream, int discard);
 
 /* ---------------------------------------------------------------------------
  * Fused Adam step over flat fp32 buffers (replaces torch.optim.Adam(lr, weight_decay=l2).step(),

@@ -22,8 +22,9 @@ SIGNATURES = {
     "mmdfn_tile_outer": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "mmdfn_adj_build": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
     "mmdfn_adj_build_bwd": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
-    "mmdfn_gru_seq_fwd": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
-    "mmdfn_gru_seq_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "mmdfn_riders_bytes": [],
+    "mmdfn_gru_seq_fwd": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
+    "mmdfn_gru_seq_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "mmdfn_gru_seq_fwd_seg": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "mmdfn_gru_seq_bwd_seg": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "mmdfn_gru_tab_reduce": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -65,15 +66,15 @@ SIGNATURES = {
     "mmdfn_gemm_tn_grouped_workspace": [_I, _P, _P, _P],
     "mmdfn_gemm_tn_grouped": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mmdfn_gemm_tn_batch_workspace": [_I, _P, _P, _I, _P, _P],
-    "mmdfn_gemm_tn_batch": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_wgrad_riders_stage": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_wgrad_riders_staged": [],
-    "mmdfn_wgrad_riders_flush": [_P],
-    "mmdfn_wgrad_riders_drain": [_P, _I],
+    "mmdfn_gemm_tn_batch": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mmdfn_wgrad_riders_stage": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mmdfn_wgrad_riders_staged": [_P],
+    "mmdfn_wgrad_riders_flush": [_P, _P],
+    "mmdfn_wgrad_riders_drain": [_P, _P, _I],
     "mmdfn_gru_seq_bwd_idle_cus": [_I, _P],
     "mmdfn_gru_seq_bwd_step_ns": [_I, _P],
     "mmdfn_gemm_tn_batch_ext": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                                _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+                                _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mmdfn_head_bwd_groups": [],
     "mmdfn_head_bwd_partial": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "mmdfn_colsum_partial": [_P, _L, _I, _I, _P, _P],
@@ -94,14 +95,14 @@ SIGNATURES = {
     "mmdfn_party_combine_bwd_dst": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mmdfn_mask_scale": [_I, _P, _P, _P, _P, _F, _P],
     "mmdfn_keep_flags": [_P, _L, _F, _P, _P],
-    "mmdfn_keep_flags_stage": [_P, _L, ctypes.c_float, _P, _P],
-    "mmdfn_keep_flags_flush": [_P],
+    "mmdfn_keep_flags_stage": [_P, _L, _F, _P, _P, _P],
+    "mmdfn_keep_flags_flush": [_P, _P],
     "mmdfn_gru_seq_fwd_takes_flags": [_I, _P],
     "mmdfn_colsum_workspace": [_I],
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class HipLibraryError(RuntimeError):
@@ -144,11 +145,17 @@ def lib():
         except AttributeError as e:
             raise HipLibraryError("%s lacks symbol %s (stale build?)" % (os.path.basename(path), name)) from e
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name.endswith("_workspace") else ctypes.c_int
+        fn.restype = ctypes.c_int64 if name.endswith(("_workspace", "_bytes")) else ctypes.c_int
     if handle.mmdfn_abi_version() != ABI_VERSION:
         raise HipLibraryError("%s ABI version mismatch" % os.path.basename(path))
     _libs[tuning] = handle
     return handle
+
+
+def riders_context():
+    """An empty rider context (include/mmdfn_hip.h mmdfn_riders_bytes): zeroed host memory that the rider entry points stage
+    work in and the GRU launches given it take work from."""
+    return ctypes.create_string_buffer(int(lib().mmdfn_riders_bytes()))
 
 
 def ptr(t):

@@ -542,13 +542,6 @@ extern "C" int mmdfn_colsum_partial(const float* A, int64_t R, int H, int lda, f
     return nsl;
 }
 
-// A draw STAGED for the next plain GRU forward launch (gru.hip: its tiles of counters run as rider workgroups of the recurrence
-// launch) instead of launched; mmdfn_keep_flags_flush launches a staged draw the ordinary way.
-static kfb::FlagJob g_flag_job;
-static bool g_flag_job_valid = false;
-const kfb::FlagJob* mmdfn_flag_job_pending() { return g_flag_job_valid ? &g_flag_job : nullptr; }
-void mmdfn_flag_job_taken() { g_flag_job_valid = false; }
-
 static int flag_job(kfb::FlagJob& J, float* out, int64_t n, float keep, void* state) {
     if (n <= 0 || (n & 3) || (reinterpret_cast<uintptr_t>(out) & 15) || state == nullptr || !(keep >= 0.f) || keep > 1.f) return -1;
     J.out = out;
@@ -577,17 +570,21 @@ extern "C" int mmdfn_keep_flags(float* out, int64_t n, float keep, void* state, 
     return launch_flag_job(J, (hipStream_t)stream);
 }
 
-extern "C" int mmdfn_keep_flags_stage(float* out, int64_t n, float keep, void* state, void* stream) {
+// A draw STAGED in a rider context for a GRU forward launch given the same context (gru.hip: its tiles of counters run as rider
+// workgroups of the recurrence launch) instead of launched; mmdfn_keep_flags_flush launches a staged draw the ordinary way.
+extern "C" int mmdfn_keep_flags_stage(float* out, int64_t n, float keep, void* state, void* riders, void* stream) {
     kfb::FlagJob J;
     if (int e = flag_job(J, out, n, keep, state)) return e;
-    if (g_flag_job_valid) return launch_flag_job(J, (hipStream_t)stream);       // one staged draw at a time: this one goes now
-    g_flag_job = J;
-    g_flag_job_valid = true;
+    MmdfnRiders* r = (MmdfnRiders*)riders;
+    if (r == nullptr || r->flag_job_valid) return launch_flag_job(J, (hipStream_t)stream);    // one staged draw at a time
+    r->flag_job = J;
+    r->flag_job_valid = true;
     return 0;
 }
 
-extern "C" int mmdfn_keep_flags_flush(void* stream) {
-    if (!g_flag_job_valid) return 0;
-    g_flag_job_valid = false;
-    return launch_flag_job(g_flag_job, (hipStream_t)stream);
+extern "C" int mmdfn_keep_flags_flush(void* riders, void* stream) {
+    MmdfnRiders* r = (MmdfnRiders*)riders;
+    if (r == nullptr || !r->flag_job_valid) return 0;
+    r->flag_job_valid = false;
+    return launch_flag_job(r->flag_job, (hipStream_t)stream);
 }

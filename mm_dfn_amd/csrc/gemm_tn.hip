@@ -254,7 +254,6 @@ __global__ void gemm_tn_grouped_reduce_kernel(const TnGroups gq) {
 //   splits of the same slab stack (the layer-shared LSTM gate gets one segment per GCN layer, the reduction sums them:
 //   no gradient-accumulation kernels).
 constexpr int TN_MAXSEG = 40;
-constexpr int TN_MAXOUT = 40;
 struct TnSegs {
     const float* A[TN_MAXSEG];
     const float* B[TN_MAXSEG];
@@ -833,26 +832,6 @@ struct TnExt {
     const int *M, *N, *ldc, *splits, *accumulate;
 };
 
-// A batch staged for the GRU backward launch (see mmdfn_internal.h): its tile table and its reduction table.
-struct RiderPlan {
-    bool valid = false;
-    TnSplitSegs tq;
-    TnOuts oq;
-    int nblk = 0;
-};
-static RiderPlan g_rider;
-
-const TnSplitSegs* mmdfn_riders_pending() { return g_rider.valid ? &g_rider.tq : nullptr; }
-
-// Slab stacks of rider batches whose reduction waits for the NEXT reduction launch of the backward pass (the end-of-backward
-// batch's, normally): a reduction launch of their own behind every recurrence costs the chain ~12 us each.
-struct DeferredOut {
-    const float* part; const float* colpart; float* C; float* colsum; float* colsum2;
-    int M, N, ldc, splits, accumulate;
-};
-static DeferredOut g_deferred[TN_MAXOUT];
-static int g_ndeferred = 0;
-
 static int reduce_blocks(int M, int N, int splits) {
     int nblk = (int)((((int64_t)M * N + M) * (splits > TN_REDUCE_WIDE ? 8 : 1) + 255) / 256);
     return nblk > 256 ? 256 : nblk;
@@ -864,22 +843,45 @@ static void put_out(TnOuts& oq, int o, const DeferredOut& d) {
     oq.blk_prefix[o + 1] = oq.blk_prefix[o] + reduce_blocks(d.M, d.N, d.splits);
 }
 
-static int launch_deferred(hipStream_t s) {
-    if (g_ndeferred == 0) return 0;
-    TnOuts oq;
-    oq.blk_prefix[0] = 0;
-    for (int o = 0; o < g_ndeferred; ++o) put_out(oq, o, g_deferred[o]);
-    oq.n = g_ndeferred;
-    for (int o = g_ndeferred; o < TN_MAXOUT; ++o) {
+static void end_outs(TnOuts& oq, int n) {      // n entries in use, the rest empty
+    oq.n = n;
+    for (int o = n; o < TN_MAXOUT; ++o) {
         oq.part[o] = oq.colpart[o] = nullptr; oq.C[o] = oq.colsum[o] = oq.colsum2[o] = nullptr;
         oq.M[o] = oq.N[o] = oq.ldc[o] = oq.splits[o] = oq.accumulate[o] = 0;
-        oq.blk_prefix[o + 1] = oq.blk_prefix[g_ndeferred];
+        oq.blk_prefix[o + 1] = oq.blk_prefix[n];
     }
-    const int nblk = oq.blk_prefix[g_ndeferred];
-    g_ndeferred = 0;
-    hipLaunchKernelGGL(gemm_tn_batch_reduce_kernel, dim3(nblk), dim3(256), 0, s, oq);
+}
+
+// one reduction launch over n outputs
+static int launch_reduce(const DeferredOut* outs, int n, hipStream_t s) {
+    if (n == 0) return 0;
+    TnOuts oq;
+    oq.blk_prefix[0] = 0;
+    for (int o = 0; o < n; ++o) put_out(oq, o, outs[o]);
+    end_outs(oq, n);
+    hipLaunchKernelGGL(gemm_tn_batch_reduce_kernel, dim3(oq.blk_prefix[n]), dim3(256), 0, s, oq);
     MMDFN_CHECK_LAUNCH();
     return 0;
+}
+
+static int launch_deferred(MmdfnRiders* r, hipStream_t s) {
+    const int n = r->ndeferred;
+    r->ndeferred = 0;
+    return launch_reduce(r->deferred, n, s);
+}
+
+// Does a waiting slab stack of the context share a destination with one of the first n outputs of oq?  (Two entries of one
+// reduction launch may not touch the same gradient: the waiting one is then reduced first, by a launch of its own.)
+static bool deferred_clash(const MmdfnRiders* r, const TnOuts& oq, int n) {
+    for (int d = 0; d < r->ndeferred; ++d)
+        for (int o = 0; o < n; ++o) {
+            const DeferredOut& q = r->deferred[d];
+            if ((q.C != nullptr && q.C == oq.C[o]) ||
+                (q.colsum != nullptr && (q.colsum == oq.colsum[o] || q.colsum == oq.colsum2[o])) ||
+                (q.colsum2 != nullptr && (q.colsum2 == oq.colsum[o] || q.colsum2 == oq.colsum2[o])))
+                return true;
+        }
+    return false;
 }
 
 static bool riders_defer_reduce() {
@@ -889,38 +891,29 @@ static bool riders_defer_reduce() {
     return true;
 }
 
-int mmdfn_riders_launched(hipStream_t s) {
-    if (!g_rider.valid) return -1;
-    g_rider.valid = false;
-    const TnOuts& oq = g_rider.oq;
-    // (two waiting stacks may not share a destination either: an earlier rider batch that wrote one of these gradients is
-    // reduced first, by a launch of its own)
-    bool clash = false;
-    for (int d = 0; d < g_ndeferred && !clash; ++d)
-        for (int o = 0; o < oq.n && !clash; ++o) {
-            const DeferredOut& q = g_deferred[d];
-            clash = (q.C != nullptr && q.C == oq.C[o]) ||
-                    (q.colsum != nullptr && (q.colsum == oq.colsum[o] || q.colsum == oq.colsum2[o])) ||
-                    (q.colsum2 != nullptr && (q.colsum2 == oq.colsum[o] || q.colsum2 == oq.colsum2[o]));
-        }
-    if (clash)
-        if (int e = launch_deferred(s)) return e;
-    if (riders_defer_reduce() && g_ndeferred + oq.n <= TN_MAXOUT) {
-        for (int o = 0; o < oq.n; ++o)
-            g_deferred[g_ndeferred++] = DeferredOut{oq.part[o], oq.colpart[o], oq.C[o], oq.colsum[o], oq.colsum2[o],
-                                                    oq.M[o], oq.N[o], oq.ldc[o], oq.splits[o], oq.accumulate[o]};
+// The tiles of the context's staged batch have been launched: its slab reduction waits in the context for the next reduction
+// launch (or goes now).
+int mmdfn_riders_launched(MmdfnRiders* r, hipStream_t s) {
+    RiderPlan& p = r->rider;
+    if (!p.valid) return -1;
+    p.valid = false;
+    TnOuts oq;
+    oq.blk_prefix[0] = 0;
+    for (int o = 0; o < p.nout; ++o) put_out(oq, o, p.outs[o]);
+    if (deferred_clash(r, oq, p.nout))
+        if (int e = launch_deferred(r, s)) return e;
+    if (riders_defer_reduce() && r->ndeferred + p.nout <= TN_MAXOUT) {
+        for (int o = 0; o < p.nout; ++o) r->deferred[r->ndeferred++] = p.outs[o];
         return 0;
     }
-    hipLaunchKernelGGL(gemm_tn_batch_reduce_kernel, dim3(g_rider.nblk), dim3(256), 0, s, g_rider.oq);
-    MMDFN_CHECK_LAUNCH();
-    return 0;
+    return launch_reduce(p.outs, p.nout, s);
 }
 
 static int tn_batch_impl(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
                          const int* ldb, const int* bshift, const int* out, int nout, float* const* C,
                          float* const* colsum, float* const* colsum2, const int* M, const int* N,
-                         const int* ldc, const int* accumulate, float* workspace, const TnExt& ext, void* stream,
-                         bool stage = false) {
+                         const int* ldc, const int* accumulate, float* workspace, const TnExt& ext, MmdfnRiders* riders,
+                         void* stream, bool stage = false) {
     if (nseg < 0 || nseg > TN_MAXSEG || nout < 0 || nout + ext.n > TN_MAXOUT || (nseg == 0) != (nout == 0) ||
         (nseg == 0 && ext.n == 0)) return -1;
     for (int e = 0; e < ext.n; ++e)
@@ -958,7 +951,7 @@ static int tn_batch_impl(int nseg, const float* const* A, const float* const* B,
     float* ws = workspace;
     float* part_base[TN_MAXOUT];
     float* col_base[TN_MAXOUT];
-    oq.n = nout;
+    DeferredOut outs[TN_MAXOUT];
     oq.blk_prefix[0] = 0;
     for (int o = 0; o < nout; ++o) {
         if (out_splits[o] == 0) return -1;   // an output nobody contributes to
@@ -966,54 +959,25 @@ static int tn_batch_impl(int nseg, const float* const* A, const float* const* B,
         ws += (int64_t)out_splits[o] * M[o] * N[o];
         col_base[o] = ws;
         ws += (int64_t)out_splits[o] * M[o];
-        oq.part[o] = part_base[o];
-        oq.colpart[o] = col_base[o];
-        oq.C[o] = C[o];
-        oq.colsum[o] = colsum ? colsum[o] : nullptr;
-        oq.colsum2[o] = colsum2 ? colsum2[o] : nullptr;
-        oq.M[o] = M[o]; oq.N[o] = N[o]; oq.ldc[o] = ldc[o]; oq.splits[o] = out_splits[o];
-        oq.accumulate[o] = accumulate ? accumulate[o] : 0;
-        int nblk = (int)((((int64_t)M[o] * N[o] + M[o]) * (out_splits[o] > TN_REDUCE_WIDE ? 8 : 1) + 255) / 256);
-        if (nblk > 256) nblk = 256;
-        oq.blk_prefix[o + 1] = oq.blk_prefix[o] + nblk;
+        outs[o] = DeferredOut{part_base[o], col_base[o], C[o], colsum ? colsum[o] : nullptr, colsum2 ? colsum2[o] : nullptr,
+                              M[o], N[o], ldc[o], out_splits[o], accumulate ? accumulate[o] : 0};
+        put_out(oq, o, outs[o]);
     }
     int ntot = nout + ext.n;
-    for (int e = 0; e < ext.n; ++e) {
-        const int o = nout + e;
-        oq.part[o] = ext.part[e]; oq.colpart[o] = ext.colpart[e];
-        oq.C[o] = ext.C[e]; oq.colsum[o] = ext.colsum[e]; oq.colsum2[o] = nullptr;
-        oq.M[o] = ext.M[e]; oq.N[o] = ext.N[e]; oq.ldc[o] = ext.ldc[e]; oq.splits[o] = ext.splits[e];
-        oq.accumulate[o] = ext.accumulate ? ext.accumulate[e] : 0;
-        const int lanes = ext.splits[e] > TN_REDUCE_WIDE ? 8 : 1;
-        int nblk = (int)((((int64_t)ext.M[e] * ext.N[e] + ext.M[e]) * lanes + 255) / 256);
-        if (nblk > 256) nblk = 256;
-        oq.blk_prefix[o + 1] = oq.blk_prefix[o] + nblk;
-    }
+    for (int e = 0; e < ext.n; ++e)
+        put_out(oq, nout + e, DeferredOut{ext.part[e], ext.colpart[e], ext.C[e], ext.colsum[e], nullptr, ext.M[e], ext.N[e],
+                                          ext.ldc[e], ext.splits[e], ext.accumulate ? ext.accumulate[e] : 0});
     // deferred slab stacks of rider batches join this launch's reduction -- unless a destination of theirs is also written here
-    // (two entries of one launch may not touch the same gradient: theirs is reduced first, by a launch of its own)
-    if (g_ndeferred > 0 && !stage) {
-        bool clash = ntot + g_ndeferred > TN_MAXOUT;
-        for (int d = 0; d < g_ndeferred && !clash; ++d)
-            for (int o = 0; o < ntot && !clash; ++o) {
-                const DeferredOut& q = g_deferred[d];
-                clash = (q.C != nullptr && q.C == oq.C[o]) ||
-                        (q.colsum != nullptr && (q.colsum == oq.colsum[o] || q.colsum == oq.colsum2[o])) ||
-                        (q.colsum2 != nullptr && (q.colsum2 == oq.colsum[o] || q.colsum2 == oq.colsum2[o]));
-            }
-        if (clash) {
-            if (int e = launch_deferred((hipStream_t)stream)) return e;
+    if (riders != nullptr && riders->ndeferred > 0 && !stage) {
+        if (ntot + riders->ndeferred > TN_MAXOUT || deferred_clash(riders, oq, ntot)) {
+            if (int e = launch_deferred(riders, (hipStream_t)stream)) return e;
         } else {
-            for (int d = 0; d < g_ndeferred; ++d) put_out(oq, ntot + d, g_deferred[d]);
-            ntot += g_ndeferred;
-            g_ndeferred = 0;
+            for (int d = 0; d < riders->ndeferred; ++d) put_out(oq, ntot + d, riders->deferred[d]);
+            ntot += riders->ndeferred;
+            riders->ndeferred = 0;
         }
     }
-    oq.n = ntot;
-    for (int o = ntot; o < TN_MAXOUT; ++o) {
-        oq.part[o] = oq.colpart[o] = nullptr; oq.C[o] = oq.colsum[o] = oq.colsum2[o] = nullptr;
-        oq.M[o] = oq.N[o] = oq.ldc[o] = oq.splits[o] = oq.accumulate[o] = 0;
-        oq.blk_prefix[o + 1] = oq.blk_prefix[ntot];
-    }
+    end_outs(oq, ntot);
     int used[TN_MAXOUT];
     for (int o = 0; o < nout; ++o) used[o] = 0;
     hipStream_t st = (hipStream_t)stream;
@@ -1051,11 +1015,12 @@ static int tn_batch_impl(int nseg, const float* const* A, const float* const* B,
             tq.M[k] = tq.N[k] = 0; tq.wide[k] = 0;
             tq.wg_prefix[k + 1] = tq.wg_prefix[nseg];
         }
-        if (stage && nseg <= MMDFN_RIDER_MAXSEG && !g_rider.valid) {
-            g_rider.tq = tq;
-            g_rider.oq = oq;
-            g_rider.nblk = oq.blk_prefix[ntot];
-            g_rider.valid = true;
+        if (stage && riders != nullptr && nseg <= MMDFN_RIDER_MAXSEG && !riders->rider.valid) {
+            RiderPlan& p = riders->rider;      // (nothing else shares this reduction: ntot = nout)
+            p.tq = tq;
+            std::copy(outs, outs + nout, p.outs);
+            p.nout = nout;
+            p.valid = true;
             return 0;
         }
         if (int e = mmdfn_launch_gemm_tn_split(tq, st)) return e;
@@ -1132,38 +1097,46 @@ static int tn_batch_impl(int nseg, const float* const* A, const float* const* B,
 extern "C" int mmdfn_gemm_tn_batch(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
                                    const int* ldb, const int* bshift, const int* out, int nout, float* const* C,
                                    float* const* colsum, float* const* colsum2, const int* M, const int* N,
-                                   const int* ldc, const int* accumulate, float* workspace, void* stream) {
+                                   const int* ldc, const int* accumulate, float* workspace, void* riders, void* stream) {
     if (nseg < 1 || nout < 1) return -1;
     const TnExt none = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, none, stream);
+    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, none,
+                         (MmdfnRiders*)riders, stream);
 }
 
-// The batch is planned as usual but NOT launched when it can ride in the next GRU backward launch (bf16-piece form, at most
-// MMDFN_RIDER_MAXSEG segments, nothing staged yet); otherwise it is launched now.  mmdfn_wgrad_riders_flush launches whatever is
-// still staged (the GRU launch that followed was of another kind, or there was none).
+extern "C" int64_t mmdfn_riders_bytes(void) { return (int64_t)sizeof(MmdfnRiders); }
+
+// The batch is planned as usual but NOT launched when it can ride in a GRU backward launch given the same context (bf16-piece
+// form, at most MMDFN_RIDER_MAXSEG segments, nothing staged in the context yet); otherwise it is launched now.
+// mmdfn_wgrad_riders_flush launches whatever is still staged (the GRU launch that followed was of another kind, or there was none).
 extern "C" int mmdfn_wgrad_riders_stage(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
                                         const int* ldb, const int* bshift, const int* out, int nout, float* const* C,
                                         float* const* colsum, float* const* colsum2, const int* M, const int* N,
-                                        const int* ldc, const int* accumulate, float* workspace, void* stream) {
+                                        const int* ldc, const int* accumulate, float* workspace, void* riders, void* stream) {
     if (nseg < 1 || nout < 1) return -1;
     const TnExt none = {0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, none, stream,
-                         true);
+    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, none,
+                         (MmdfnRiders*)riders, stream, true);
 }
 
-extern "C" int mmdfn_wgrad_riders_staged() { return g_rider.valid ? 1 : 0; }
+extern "C" int mmdfn_wgrad_riders_staged(void* riders) {
+    return riders != nullptr && ((MmdfnRiders*)riders)->rider.valid ? 1 : 0;
+}
 
 // End of the backward pass: slab stacks of rider batches that no later reduction launch took are reduced now (discard != 0:
 // forgotten instead -- a backward pass that raised left them behind).
-extern "C" int mmdfn_wgrad_riders_drain(void* stream, int discard) {
-    if (discard) { g_ndeferred = 0; g_rider.valid = false; return 0; }
-    return launch_deferred((hipStream_t)stream);
+extern "C" int mmdfn_wgrad_riders_drain(void* riders, void* stream, int discard) {
+    MmdfnRiders* r = (MmdfnRiders*)riders;
+    if (r == nullptr) return 0;
+    if (discard) { r->ndeferred = 0; r->rider.valid = false; return 0; }
+    return launch_deferred(r, (hipStream_t)stream);
 }
 
-extern "C" int mmdfn_wgrad_riders_flush(void* stream) {
-    if (!g_rider.valid) return 0;
-    if (int e = mmdfn_launch_gemm_tn_split(g_rider.tq, (hipStream_t)stream)) { g_rider.valid = false; return e; }
-    return mmdfn_riders_launched((hipStream_t)stream);
+extern "C" int mmdfn_wgrad_riders_flush(void* riders, void* stream) {
+    MmdfnRiders* r = (MmdfnRiders*)riders;
+    if (r == nullptr || !r->rider.valid) return 0;
+    if (int e = mmdfn_launch_gemm_tn_split(r->rider.tq, (hipStream_t)stream)) { r->rider.valid = false; return e; }
+    return mmdfn_riders_launched(r, (hipStream_t)stream);
 }
 
 extern "C" int mmdfn_gemm_tn_batch_ext(int nseg, const float* const* A, const float* const* B, const int* R, const int* lda,
@@ -1172,9 +1145,10 @@ extern "C" int mmdfn_gemm_tn_batch_ext(int nseg, const float* const* A, const fl
                                        const int* ldc, const int* accumulate, float* workspace, int next,
                                        const float* const* ext_part, const float* const* ext_colpart, float* const* ext_C,
                                        float* const* ext_colsum, const int* ext_M, const int* ext_N, const int* ext_ldc,
-                                       const int* ext_splits, const int* ext_accumulate, void* stream) {
+                                       const int* ext_splits, const int* ext_accumulate, void* riders, void* stream) {
     if (next < 0 || (next > 0 && (!ext_part || !ext_colpart || !ext_C || !ext_colsum || !ext_M || !ext_N || !ext_ldc || !ext_splits)))
         return -1;
     const TnExt ext = {next, ext_part, ext_colpart, ext_C, ext_colsum, ext_M, ext_N, ext_ldc, ext_splits, ext_accumulate};
-    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, ext, stream);
+    return tn_batch_impl(nseg, A, B, R, lda, ldb, bshift, out, nout, C, colsum, colsum2, M, N, ldc, accumulate, workspace, ext,
+                         (MmdfnRiders*)riders, stream);
 }

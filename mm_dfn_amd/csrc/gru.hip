@@ -1724,9 +1724,26 @@ int pick_r(int ngroups, const int* rows) {
 
 }  // namespace
 
+GruForm mmdfn_gru_form(int ngroups, const int* rows) {
+    GruForm f = {false, 1, 0, 0};
+    if (ngroups <= 0 || ngroups > MAXG) return f;
+    int chains = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        if (rows[g] <= 0) return f;
+        chains += 2 * rows[g];
+    }
+    f.R = pick_r(ngroups, rows);
+    f.mfma = chains > mfma_min_chains();
+    const int per_wg = f.mfma ? 16 : f.R;          // sequences per workgroup (gru_mfma.hip: 16)
+    for (int g = 0; g < ngroups; ++g) f.slices += (rows[g] + per_wg - 1) / per_wg;
+    // riders need a launch of one round with CUs to spare: the MFMA form, or one sequence per workgroup
+    if ((f.mfma || f.R == 1) && 2 * f.slices < MMDFN_CUS) f.idle_cus = MMDFN_CUS - 2 * f.slices;
+    return f;
+}
+
 extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const float* const* w_hh,
                                  const float* const* b_hh, float* const* y, float* const* gates, const int* rows,
-                                 const int* T, int H, void* stream) {
+                                 const int* T, int H, void* riders, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
     FwdGroups G;
     G.n = ngroups;
@@ -1734,7 +1751,8 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_ABL")) G.abl = atoi(e);
 #endif
-    const int R = pick_r(ngroups, rows);
+    const GruForm f = mmdfn_gru_form(ngroups, rows);
+    const int R = f.R;
     int sl = 0;
     for (int g = 0; g < ngroups; ++g) {
         if (rows[g] <= 0 || T[g] <= 0) return -1;
@@ -1747,15 +1765,12 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
     G.slice0[ngroups] = sl;
     dim3 grid(sl, 2), block(NT);
     hipStream_t s = (hipStream_t)stream;
-    {
-        int chains = 0;
-        for (int g = 0; g < ngroups; ++g) chains += 2 * rows[g];
-        if (chains > mfma_min_chains() && G.abl == 0) return mmdfn_launch_gru_fwd_mfma(ngroups, gi, w_hh, b_hh, y, gates, rows, T, s);
-    }
+    MmdfnRiders* rd = (MmdfnRiders*)riders;
+    if (f.mfma && G.abl == 0) return mmdfn_launch_gru_fwd_mfma(f, ngroups, gi, w_hh, b_hh, y, gates, rows, T, rd, s);
     // the 5-wave kernel runs one workgroup per CU (its fifth wave shares a SIMD with a recurrence wave at ~210 VGPRs each):
     // it wins while every sequence gets a CU of its own in one round (cfg2: 160 workgroups); beyond that the 4-wave kernel,
     // two workgroups per CU, needs fewer rounds (cfg3 / cfg4: +4-5 % step time with the 5-wave kernel, measured)
-    bool io_wave = (R == 1) && (2 * sl <= 256);
+    bool io_wave = (R == 1) && (2 * sl <= MMDFN_CUS);
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_IO")) io_wave = io_wave && e[0] != '0';      // A/B aid
 #endif
@@ -1768,17 +1783,15 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
     GRU_IO_ABL(1) GRU_IO_ABL(2) GRU_IO_ABL(4) GRU_IO_ABL(8) GRU_IO_ABL(16) GRU_IO_ABL(3) GRU_IO_ABL(11) GRU_IO_ABL(31) GRU_IO_ABL(23) GRU_IO_ABL(64)
 #undef GRU_IO_ABL
 #endif
-    if (io_wave && !scalar_fma && 2 * sl < 256) {
-        if (const kfb::FlagJob* fj = mmdfn_flag_job_pending()) {
-            // a staged dropout-flag draw rides on the CUs this launch leaves idle (gru_seq_fwd_io_flags_kernel)
-            int64_t nr = (fj->n8 + 319) / 320;
-            if (nr > 256 - 2 * sl) nr = 256 - 2 * sl;
-            const kfb::FlagJob J = *fj;
-            mmdfn_flag_job_taken();
-            hipLaunchKernelGGL(gru_seq_fwd_io_flags_kernel, dim3(2 * sl + (int)nr), dim3(320), 0, s, G, J, sl);
-            MMDFN_CHECK_LAUNCH();
-            return 0;
-        }
+    if (io_wave && !scalar_fma && f.idle_cus > 0 && rd != nullptr && rd->flag_job_valid) {
+        // a staged dropout-flag draw rides on the CUs this launch leaves idle (gru_seq_fwd_io_flags_kernel)
+        const kfb::FlagJob J = rd->flag_job;
+        rd->flag_job_valid = false;
+        int64_t nr = (J.n8 + 319) / 320;
+        if (nr > f.idle_cus) nr = f.idle_cus;
+        hipLaunchKernelGGL(gru_seq_fwd_io_flags_kernel, dim3(2 * sl + (int)nr), dim3(320), 0, s, G, J, sl);
+        MMDFN_CHECK_LAUNCH();
+        return 0;
     }
     if (io_wave && scalar_fma) hipLaunchKernelGGL((gru_seq_fwd_io_kernel<1, 0, 0>), grid, dim3(320), 0, s, G);
     else if (io_wave) hipLaunchKernelGGL((gru_seq_fwd_io_kernel<0, 0, 0>), grid, dim3(320), 0, s, G);
@@ -1791,11 +1804,12 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
 
 extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const float* const* y,
                                  const float* const* gates, const float* const* w_hh, float* const* dgi,
-                                 float* const* dgh, const int* rows, const int* T, int H, void* stream) {
+                                 float* const* dgh, const int* rows, const int* T, int H, void* riders, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
     BwdGroups G;
     G.n = ngroups;
-    const int R = pick_r(ngroups, rows);
+    const GruForm f = mmdfn_gru_form(ngroups, rows);
+    const int R = f.R;
     int sl = 0;
     for (int g = 0; g < ngroups; ++g) {
         if (rows[g] <= 0 || T[g] <= 0) return -1;
@@ -1807,25 +1821,20 @@ extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const floa
     G.slice0[ngroups] = sl;
     dim3 grid(sl, 2), block(NT);
     hipStream_t s = (hipStream_t)stream;
-    {
-        int chains = 0;
-        for (int g = 0; g < ngroups; ++g) chains += 2 * rows[g];
-        if (chains > mfma_min_chains()) return mmdfn_launch_gru_bwd_mfma(ngroups, dy, y, gates, w_hh, dgi, dgh, rows, T, s);
-    }
+    MmdfnRiders* rd = (MmdfnRiders*)riders;
+    if (f.mfma) return mmdfn_launch_gru_bwd_mfma(f, ngroups, dy, y, gates, w_hh, dgi, dgh, rows, T, rd, s);
     // (the 8-wave kernel runs one workgroup per CU: it wins while all sequences fit in one round; beyond that the lane-pair
     // kernel, two workgroups per CU, keeps the batch in one round -- cfg4: 320 workgroups, 1.75 vs 1.69 ms per step)
-    if (R == 1 && (2 * sl <= 256 || kpart_any_size()) && use_kpart_bwd()) {
-        if (const TnSplitSegs* rp = mmdfn_riders_pending()) {
+    if (R == 1 && (2 * sl <= MMDFN_CUS || kpart_any_size()) && use_kpart_bwd()) {
+        if (f.idle_cus > 0 && rd != nullptr && rd->rider.valid && rd->rider.tq.n <= MMDFN_RIDER_MAXSEG) {
             // a staged weight-gradient batch rides on the CUs this launch leaves idle (gru_seq_bwd_riders_kernel)
-            if (rp->n <= MMDFN_RIDER_MAXSEG && 2 * sl < 256) {
-                const TnRiderSegs rq = mmdfn_rider_table(*rp);
-                const int ngru8 = (2 * sl + 7) & ~7;
-                if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel)) return e;
-                hipLaunchKernelGGL(gru_seq_bwd_riders_kernel, dim3(ngru8 + rp->wg_prefix[rp->n]), dim3(512), tnsb::LDS_B, s, G, rq, sl,
-                                   ngru8);
-                MMDFN_CHECK_LAUNCH();
-                return mmdfn_riders_launched(s);
-            }
+            const TnSplitSegs& rp = rd->rider.tq;
+            const TnRiderSegs rq = mmdfn_rider_table(rp);
+            const int ngru8 = (2 * sl + 7) & ~7;
+            if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel)) return e;
+            hipLaunchKernelGGL(gru_seq_bwd_riders_kernel, dim3(ngru8 + rp.wg_prefix[rp.n]), dim3(512), tnsb::LDS_B, s, G, rq, sl, ngru8);
+            MMDFN_CHECK_LAUNCH();
+            return mmdfn_riders_launched(rd, s);
         }
         hipLaunchKernelGGL((gru_seq_bwd_kpart_kernel<8, 4, 0>), grid, dim3(512), 0, s, G);
     }
@@ -1837,49 +1846,21 @@ extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const floa
 }
 
 // CUs the plain backward launch of these groups would leave idle IF it is of the kind that takes weight-gradient riders (one
-// sequence per workgroup on the wave-partitioned kernel, fewer workgroups than CUs); 0 otherwise.  The host stages a rider
-// batch (mmdfn_wgrad_riders_stage) only in front of such a launch, and sizes it by this number.
+// sequence per workgroup on the wave-partitioned kernel, or the MFMA form, fewer workgroups than CUs); 0 otherwise.  The host
+// stages a rider batch (mmdfn_wgrad_riders_stage) only in front of such a launch, and sizes it by this number.
 extern "C" int mmdfn_gru_seq_bwd_idle_cus(int ngroups, const int* rows) {
-    if (ngroups <= 0 || ngroups > MAXG) return 0;
-    const int R = pick_r(ngroups, rows);
-    int sl = 0, chains = 0;
-    for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0) return 0;
-        sl += (rows[g] + R - 1) / R;
-        chains += 2 * rows[g];
-    }
-    if (chains > mfma_min_chains()) {           // the MFMA form: 16 sequences per workgroup (gru_mfma.hip)
-        int slm = 0;
-        for (int g = 0; g < ngroups; ++g) slm += (rows[g] + 15) / 16;
-        return 2 * slm < 256 ? 256 - 2 * slm : 0;
-    }
-    if (R == 1 && 2 * sl < 256 && use_kpart_bwd()) return 256 - 2 * sl;
-    return 0;
+    const GruForm f = mmdfn_gru_form(ngroups, rows);
+    return (f.mfma || use_kpart_bwd()) ? f.idle_cus : 0;
 }
 
 // 1 if the plain FORWARD launch of these groups is of the kind that carries a staged dropout-flag draw (mmdfn_keep_flags_stage)
 extern "C" int mmdfn_gru_seq_fwd_takes_flags(int ngroups, const int* rows) {
-    if (ngroups <= 0 || ngroups > MAXG) return 0;
-    const int R = pick_r(ngroups, rows);
-    int sl = 0, chains = 0;
-    for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0) return 0;
-        sl += (rows[g] + R - 1) / R;
-        chains += 2 * rows[g];
-    }
-    if (chains > mfma_min_chains()) {           // the MFMA form: 16 sequences per workgroup (gru_mfma.hip)
-        int slm = 0;
-        for (int g = 0; g < ngroups; ++g) slm += (rows[g] + 15) / 16;
-        return 2 * slm < 256 ? 1 : 0;
-    }
-    return (R == 1 && 2 * sl < 256) ? 1 : 0;
+    return mmdfn_gru_form(ngroups, rows).idle_cus > 0 ? 1 : 0;
 }
 
 // nanoseconds per recurrence step of that launch (what the rider batch's size is priced with)
 extern "C" int mmdfn_gru_seq_bwd_step_ns(int ngroups, const int* rows) {
-    int chains = 0;
-    for (int g = 0; g < ngroups && g < MAXG; ++g) chains += 2 * rows[g];
-    return chains > mfma_min_chains() ? 2300 : 750;
+    return mmdfn_gru_form(ngroups, rows).mfma ? 2300 : 750;
 }
 
 extern "C" int mmdfn_gru_seq_fwd_seg(int ngroups, const float* const* gi, const float* const* w_hh,
@@ -1902,7 +1883,7 @@ extern "C" int mmdfn_gru_seq_fwd_seg(int ngroups, const float* const* gi, const 
     const int nchains = seg_slots(G.seg, ngroups, rows, T, rank, P, BP, tdir);
     if (nchains <= 0) return -1;
     // one chain per CU: the 5-wave kernel (one workgroup per CU); more chains: the 4-wave kernel, two workgroups per CU
-    bool io_wave = nchains <= 256;
+    bool io_wave = nchains <= MMDFN_CUS;
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_IO")) io_wave = e[0] != '0';      // A/B aid
 #endif
@@ -1940,7 +1921,7 @@ extern "C" int mmdfn_gru_seq_bwd_seg(int ngroups, const float* const* dy, const 
     }
     const int nchains = seg_slots(G.seg, ngroups, rows, T, rank, P, BP, tdir);
     if (nchains <= 0) return -1;
-    bool kpart = nchains <= 256;
+    bool kpart = nchains <= MMDFN_CUS;
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_KPART_BWD")) kpart = e[0] != '0';      // A/B aid
 #endif

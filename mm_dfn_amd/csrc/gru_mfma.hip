@@ -510,8 +510,9 @@ __global__ __launch_bounds__(BWD_THREADS) void gru_seq_bwd_mfma_riders_kernel(co
 
 }  // namespace
 
-int mmdfn_launch_gru_fwd_mfma(int ngroups, const float* const* gi, const float* const* w_hh, const float* const* b_hh,
-                              float* const* y, float* const* gates, const int* rows, const int* T, hipStream_t s) {
+int mmdfn_launch_gru_fwd_mfma(const GruForm& f, int ngroups, const float* const* gi, const float* const* w_hh,
+                              const float* const* b_hh, float* const* y, float* const* gates, const int* rows, const int* T,
+                              MmdfnRiders* riders, hipStream_t s) {
     if (ngroups <= 0 || ngroups > MAXG) return -2;
     MfFwd G;
     G.n = ngroups;
@@ -530,18 +531,16 @@ int mmdfn_launch_gru_fwd_mfma(int ngroups, const float* const* gi, const float* 
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_MF_ABL")) G.abl = atoi(e);
 #endif
-    if (G.abl == 0 && 2 * sl < 256) {
-        if (const kfb::FlagJob* fj = mmdfn_flag_job_pending()) {
-            // a staged dropout-flag draw rides on the CUs this launch leaves idle
-            int64_t nr = (fj->n8 + FWD_THREADS - 1) / FWD_THREADS;
-            if (nr > 256 - 2 * sl) nr = 256 - 2 * sl;
-            const kfb::FlagJob J = *fj;
-            mmdfn_flag_job_taken();
-            if (int e = mmdfn_allow_big_lds(gru_seq_fwd_mfma_flags_kernel)) return e;
-            hipLaunchKernelGGL(gru_seq_fwd_mfma_flags_kernel, dim3(2 * sl + (int)nr), dim3(FWD_THREADS), FWD_LDS, s, G, J, sl);
-            MMDFN_CHECK_LAUNCH();
-            return 0;
-        }
+    if (G.abl == 0 && f.idle_cus > 0 && riders != nullptr && riders->flag_job_valid) {
+        // a staged dropout-flag draw rides on the CUs this launch leaves idle
+        const kfb::FlagJob J = riders->flag_job;
+        riders->flag_job_valid = false;
+        int64_t nr = (J.n8 + FWD_THREADS - 1) / FWD_THREADS;
+        if (nr > f.idle_cus) nr = f.idle_cus;
+        if (int e = mmdfn_allow_big_lds(gru_seq_fwd_mfma_flags_kernel)) return e;
+        hipLaunchKernelGGL(gru_seq_fwd_mfma_flags_kernel, dim3(2 * sl + (int)nr), dim3(FWD_THREADS), FWD_LDS, s, G, J, sl);
+        MMDFN_CHECK_LAUNCH();
+        return 0;
     }
     if (int e = mmdfn_allow_big_lds(gru_seq_fwd_mfma_kernel)) return e;
     hipLaunchKernelGGL(gru_seq_fwd_mfma_kernel, dim3(sl, 2), dim3(FWD_THREADS), FWD_LDS, s, G);
@@ -549,9 +548,9 @@ int mmdfn_launch_gru_fwd_mfma(int ngroups, const float* const* gi, const float* 
     return 0;
 }
 
-int mmdfn_launch_gru_bwd_mfma(int ngroups, const float* const* dy, const float* const* y, const float* const* gates,
-                              const float* const* w_hh, float* const* dgi, float* const* dgh, const int* rows, const int* T,
-                              hipStream_t s) {
+int mmdfn_launch_gru_bwd_mfma(const GruForm& f, int ngroups, const float* const* dy, const float* const* y,
+                              const float* const* gates, const float* const* w_hh, float* const* dgi, float* const* dgh,
+                              const int* rows, const int* T, MmdfnRiders* riders, hipStream_t s) {
     if (ngroups <= 0 || ngroups > MAXG) return -2;
     MfBwd G;
     G.n = ngroups;
@@ -567,17 +566,16 @@ int mmdfn_launch_gru_bwd_mfma(int ngroups, const float* const* dy, const float* 
     G.slice0[MAXG] = sl;
     for (int g = ngroups; g < MAXG; ++g) G.slice0[g] = sl;
     G.abl = 0;
-    if (const TnSplitSegs* rp = mmdfn_riders_pending()) {
+    if (f.idle_cus > 0 && riders != nullptr && riders->rider.valid && riders->rider.tq.n <= MMDFN_RIDER_MAXSEG) {
         // a staged weight-gradient batch rides on the CUs this launch leaves idle
-        if (rp->n <= MMDFN_RIDER_MAXSEG && 2 * sl < 256) {
-            const TnRiderSegs rq = mmdfn_rider_table(*rp);
-            const int ngru8 = (2 * sl + 7) & ~7;
-            if (int e = mmdfn_allow_big_lds(gru_seq_bwd_mfma_riders_kernel)) return e;
-            hipLaunchKernelGGL(gru_seq_bwd_mfma_riders_kernel, dim3(ngru8 + rp->wg_prefix[rp->n]), dim3(BWD_THREADS), BWD_LDS, s, G, rq,
-                               sl, ngru8);
-            MMDFN_CHECK_LAUNCH();
-            return mmdfn_riders_launched(s);
-        }
+        const TnSplitSegs& rp = riders->rider.tq;
+        const TnRiderSegs rq = mmdfn_rider_table(rp);
+        const int ngru8 = (2 * sl + 7) & ~7;
+        if (int e = mmdfn_allow_big_lds(gru_seq_bwd_mfma_riders_kernel)) return e;
+        hipLaunchKernelGGL(gru_seq_bwd_mfma_riders_kernel, dim3(ngru8 + rp.wg_prefix[rp.n]), dim3(BWD_THREADS), BWD_LDS, s, G, rq, sl,
+                           ngru8);
+        MMDFN_CHECK_LAUNCH();
+        return mmdfn_riders_launched(riders, s);
     }
     if (int e = mmdfn_allow_big_lds(gru_seq_bwd_mfma_kernel)) return e;
     hipLaunchKernelGGL(gru_seq_bwd_mfma_kernel, dim3(sl, 2), dim3(BWD_THREADS), BWD_LDS, s, G);

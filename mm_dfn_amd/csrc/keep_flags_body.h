@@ -7,14 +7,6 @@
 
 namespace kfb {
 
-struct FlagJob {
-    float* out;
-    int64_t n8, n4;
-    uint32_t threshold;
-    int all;
-    unsigned long long* state;
-};
-
 __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
     constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll
@@ -69,7 +61,3 @@ __device__ __forceinline__ void keep_flags_block(const FlagJob& J, const int bid
 }
 
 }  // namespace kfb
-
-// (encoder_glue.hip) the draw staged by mmdfn_keep_flags_stage, or nullptr; the launch that ran it says so
-const kfb::FlagJob* mmdfn_flag_job_pending();
-void mmdfn_flag_job_taken();

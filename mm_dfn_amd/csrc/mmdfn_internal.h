@@ -15,6 +15,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MMDFN_COS_SHRINK 0.99999f
 #define MMDFN_PI_F 3.14159265358979323846f
 
+// compute units of the target (gfx950 / MI355X): what the GRU launches' rider sizing counts idle CUs against
+constexpr int MMDFN_CUS = 256;
+
 __device__ __forceinline__ float mmdfn_sim(float c) {
     return 1.0f - acosf(c * MMDFN_COS_SHRINK) / MMDFN_PI_F;
 }
@@ -145,10 +148,11 @@ struct TnSplitSegs {
 };
 int mmdfn_launch_gemm_tn_split(const TnSplitSegs& sq, hipStream_t s);
 
-// Riders of the GRU backward launch (gru.hip, gru_seq_bwd_riders_kernel): a weight-gradient batch STAGED by
-// mmdfn_wgrad_riders_stage (gemm_tn.hip) instead of launched; the next plain GRU backward launch of the one-sequence-per-workgroup
-// kind runs its tiles as extra workgroups on the CUs the recurrence leaves idle, then calls mmdfn_riders_launched (the slab
-// reduction).  Whatever is still pending when the host asks (mmdfn_wgrad_riders_flush) is launched the ordinary way.
+// Riders of the GRU recurrence launches (gru.hip, gru_mfma.hip): work STAGED in a caller-owned MmdfnRiders context instead of
+// launched -- a weight-gradient batch (mmdfn_wgrad_riders_stage, gemm_tn.hip) or a dropout-flag draw (mmdfn_keep_flags_stage,
+// encoder_glue.hip).  A GRU backward / forward launch given the context runs what it holds as extra workgroups on the CUs the
+// recurrence leaves idle; mmdfn_riders_launched then files the batch's slab reduction.  What a launch did not take is launched
+// the ordinary way by mmdfn_wgrad_riders_flush / mmdfn_keep_flags_flush.
 constexpr int MMDFN_RIDER_MAXSEG = 16;
 struct TnRiderSegs {
     const float* A[MMDFN_RIDER_MAXSEG];
@@ -175,13 +179,54 @@ inline TnRiderSegs mmdfn_rider_table(const TnSplitSegs& t) {      // (t.n <= MMD
     rq.n = t.n;
     return rq;
 }
-const TnSplitSegs* mmdfn_riders_pending();
-int mmdfn_riders_launched(hipStream_t s);
+
+constexpr int TN_MAXOUT = 40;      // outputs of one weight-gradient batch's reduction launch (gemm_tn.hip)
+namespace kfb {
+struct FlagJob {            // one dropout keep-flag draw (keep_flags_body.h)
+    float* out;
+    int64_t n8, n4;
+    uint32_t threshold;
+    int all;
+    unsigned long long* state;
+};
+}  // namespace kfb
+
+// One output of a weight-gradient batch's slab reduction: `splits` slabs summed into C / colsum / colsum2 (gemm_tn.hip).
+struct DeferredOut {
+    const float* part; const float* colpart; float* C; float* colsum; float* colsum2;
+    int M, N, ldc, splits, accumulate;
+};
+// A batch staged for a GRU backward launch: its tile table and the outputs of its slab reduction.
+struct RiderPlan {
+    bool valid;
+    TnSplitSegs tq;
+    DeferredOut outs[TN_MAXOUT];
+    int nout;
+};
+// The rider context (mmdfn_riders_bytes): host memory owned by the caller, all-zero bytes = empty.
+struct MmdfnRiders {
+    RiderPlan rider;
+    DeferredOut deferred[TN_MAXOUT];      // slab reductions of batches that rode, waiting for the next reduction launch
+    int ndeferred;
+    kfb::FlagJob flag_job;
+    bool flag_job_valid;
+};
+int mmdfn_riders_launched(MmdfnRiders* riders, hipStream_t s);
+
+// How the plain (unsegmented) recurrence launch of these groups runs: the MFMA form (16 sequences per workgroup) or R sequences
+// per workgroup, `slices` workgroups per direction, and the CUs it leaves idle for riders (0: it takes none).  The launches and
+// the query entry points all read it.
+struct GruForm {
+    bool mfma;
+    int R, slices, idle_cus;
+};
+GruForm mmdfn_gru_form(int ngroups, const int* rows);
 
 // MFMA form of the GRU recurrence for launches with very many sequences (gru_mfma.hip): 16 sequences per workgroup, the
 // recurrent products on bf16 pieces.  Same operands and layouts as mmdfn_gru_seq_fwd / _bwd; -2 = not covered.
-int mmdfn_launch_gru_fwd_mfma(int ngroups, const float* const* gi, const float* const* w_hh, const float* const* b_hh,
-                              float* const* y, float* const* gates, const int* rows, const int* T, hipStream_t s);
-int mmdfn_launch_gru_bwd_mfma(int ngroups, const float* const* dy, const float* const* y, const float* const* gates,
-                              const float* const* w_hh, float* const* dgi, float* const* dgh, const int* rows, const int* T,
-                              hipStream_t s);
+int mmdfn_launch_gru_fwd_mfma(const GruForm& f, int ngroups, const float* const* gi, const float* const* w_hh,
+                              const float* const* b_hh, float* const* y, float* const* gates, const int* rows, const int* T,
+                              MmdfnRiders* riders, hipStream_t s);
+int mmdfn_launch_gru_bwd_mfma(const GruForm& f, int ngroups, const float* const* dy, const float* const* y,
+                              const float* const* gates, const float* const* w_hh, float* const* dgi, float* const* dgh,
+                              const int* rows, const int* T, MmdfnRiders* riders, hipStream_t s);

@@ -60,17 +60,15 @@ class _Seg:
         return _hip.ptr_array(ranks), _hip.int_array(P), _hip.int_array(BP), _hip.int_array(tdir)
 
 
-_FLAG_RIDER_P = [None]     # bigru2 -> _GruRecurrence.forward: the dropout rate whose flags the NEXT plain forward launch may carry
-
-
 class _GruRecurrence(torch.autograd.Function):
-    """args = (seg, ytab, then per group (gi, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev), flattened) -> (y_0, y_1, ...).  The
-    recurrent weights are the module's own parameters (no stack / cat per step): the kernels take one pointer per direction
+    """args = (seg, ytab, flag_p, then per group (gi, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev), flattened) -> (y_0, y_1, ...).
+    The recurrent weights are the module's own parameters (no stack / cat per step): the kernels take one pointer per direction
     and the gradients come back per parameter.  ``seg`` (a _Seg or None) selects the segmented launch; ``ytab`` (T, 1, 2H) or
-    None: the all-padding sequence's outputs the truncated reverse direction starts from (its gradient is returned)."""
+    None: the all-padding sequence's outputs the truncated reverse direction starts from (its gradient is returned);
+    ``flag_p`` (or None): the dropout rate whose keep flags the plain forward launch may draw as riders."""
 
     @staticmethod
-    def forward(ctx, seg, ytab, *args):
+    def forward(ctx, seg, ytab, flag_p, *args):
         n = len(args) // 5
         gis = [args[5 * g].contiguous() for g in range(n)]
         whh = [args[5 * g + 1 + d].contiguous() for g in range(n) for d in range(2)]
@@ -86,16 +84,17 @@ class _GruRecurrence(torch.autograd.Function):
             Ts.append(T)
         if seg is None:
             # (the first layer of a training-mode bigru2: the step's dropout flags are drawn as riders of this launch)
-            flag_p, _FLAG_RIDER_P[0] = _FLAG_RIDER_P[0], None
+            riders = None
             if flag_p is not None:
-                ops.stage_flag_draw(flag_p, gis[0].device, rows)
+                riders = _hip.riders_context()
+                ops.stage_flag_draw(flag_p, gis[0].device, rows, riders)
             try:
                 rc = _hip.lib().mmdfn_gru_seq_fwd(n, _hip.ptr_array(gis), _hip.ptr_array(whh), _hip.ptr_array(bhh),
                                                   _hip.ptr_array(ys), _hip.ptr_array(gates), _hip.int_array(rows),
-                                                  _hip.int_array(Ts), H, _hip.stream())
+                                                  _hip.int_array(Ts), H, riders, _hip.stream())
             finally:
-                if flag_p is not None:
-                    ops.finish_flag_draw()
+                if riders is not None:
+                    ops.finish_flag_draw(riders)
             _hip.check(rc, "mmdfn_gru_seq_fwd")
         else:
             if ytab is not None:
@@ -130,11 +129,11 @@ class _GruRecurrence(torch.autograd.Function):
         dyt = None
         if seg is None:
             # weight gradients queued so far ride on the CUs this recurrence leaves idle (ops_wgrad.stage_riders)
-            ops.stage_riders(rows, Ts)
+            riders = ops.stage_riders(rows, Ts)
             try:
                 rc = _hip.lib().mmdfn_gru_seq_bwd(n, _hip.ptr_array(dys), _hip.ptr_array(ys), _hip.ptr_array(gates),
                                                   _hip.ptr_array(whh), _hip.ptr_array(dgi), _hip.ptr_array(dgh),
-                                                  _hip.int_array(rows), _hip.int_array(Ts), H, _hip.stream())
+                                                  _hip.int_array(rows), _hip.int_array(Ts), H, riders, _hip.stream())
             finally:
                 ops.finish_riders()
             _hip.check(rc, "mmdfn_gru_seq_bwd")
@@ -178,7 +177,7 @@ class _GruRecurrence(torch.autograd.Function):
                     ops.gemm_tn_grouped([dict(A=A, B=B, C=dw, colsum=db, shift=shift)])
                     res.append((dw, db))
             out += [dgi[g], res[0][0], res[1][0], res[0][1], res[1][1]]
-        return (None, dyt) + tuple(out)
+        return (None, dyt, None) + tuple(out)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -237,7 +236,7 @@ class _GruTable(torch.autograd.Function):
         gates = torch.empty(T, 1, 2, 4, H, dtype=torch.float32, device=gi.device)
         rc = _hip.lib().mmdfn_gru_seq_fwd(1, _hip.ptr_array([gi]), _hip.ptr_array(whh), _hip.ptr_array(bhh),
                                           _hip.ptr_array([y]), _hip.ptr_array([gates]), _hip.int_array([1]),
-                                          _hip.int_array([T]), H, _hip.stream())
+                                          _hip.int_array([T]), H, None, _hip.stream())
         _hip.check(rc, "mmdfn_gru_seq_fwd")
         ctx.T = T
         ctx.params = params            # (b_ih_rev, w_hh_rev, b_hh_rev): the parameter objects themselves
@@ -253,7 +252,7 @@ class _GruTable(torch.autograd.Function):
         dgh = torch.empty_like(dgi)
         rc = _hip.lib().mmdfn_gru_seq_bwd(1, _hip.ptr_array([dy]), _hip.ptr_array([y]), _hip.ptr_array([gates]),
                                           _hip.ptr_array([wf, wr]), _hip.ptr_array([dgi]), _hip.ptr_array([dgh]),
-                                          _hip.int_array([1]), _hip.int_array([T]), H, _hip.stream())
+                                          _hip.int_array([1]), _hip.int_array([T]), H, None, _hip.stream())
         _hip.check(rc, "mmdfn_gru_seq_bwd")
         bir, w, b = ctx.params
         d2, g2, y2 = dgh.view(T, 6 * H)[:, 3 * H:], dgi.view(T, 6 * H)[:, 3 * H:], y.view(T, 2 * H)[:, H:]
@@ -412,19 +411,18 @@ def bigru2(xs, grus, dropout=0.0, training=False, gi0=None, party=None):
         args = []
         for gi, p in zip(gis, prm):
             args += [gi] + p[2]
-        _FLAG_RIDER_P[0] = dropout if (layer == 0 and training and dropout > 0) else None
+        fp = dropout if (layer == 0 and training and dropout > 0) else None
         if party is None:
-            cur = list(_GruRecurrence.apply(None, None, *args))
+            cur = list(_GruRecurrence.apply(None, None, fp, *args))
         elif layer == 0 and party[2] is None and not L1_SKIPS_SILENT:
-            cur = list(_GruRecurrence.apply(None, None, *args))
+            cur = list(_GruRecurrence.apply(None, None, fp, *args))
         elif layer == 0 and party[2] is None:
             # no all-padding sequence at hand: layer 1 runs both directions at full length, silent rows are skipped
-            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], -1), None, *args))
+            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], -1), None, fp, *args))
         elif layer == 0:
-            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], 1), party[2].join(), *args))
+            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], 1), party[2].join(), fp, *args))
         else:
-            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], 0), None, *args))
-        _FLAG_RIDER_P[0] = None
+            cur = list(_GruRecurrence.apply(_Seg(party[0], party[1], 0), None, fp, *args))
         if layer == 0 and training and dropout > 0:
             # nn.GRU's dropout between the layers: 0 / 1 keep flags from the step's flag pool (no generator launch of its
             # own) applied to every group's output by ONE launch each way -- at the head of the next layer (see there)

@@ -106,15 +106,15 @@ def flags_advance_host(idx, counters):
 # generator launch (7.7 us at cfg2, a link of the step's dependent chain) runs as extra workgroups of the recurrence launch
 # instead (csrc/gru.hip gru_seq_fwd_io_flags_kernel, include/mmdfn_hip.h mmdfn_keep_flags_stage).
 FLAG_RIDER = __import__("os").environ.get("MMDFN_FLAG_RIDER", "1") == "1"
-_FLAG_STAGED = [False]
 
 
-def stage_flag_draw(p, device, rows):
+def stage_flag_draw(p, device, rows, riders):
     """In front of the plain forward launch of the first GRU layer (groups of ``rows`` sequences): if the step's flag pool has no
     buffer for (device, p) yet and the previous step with the same scope key says how many flags the step uses, draw them NOW
-    as riders of that launch.  ``finish_flag_draw()`` must follow the launch."""
+    as riders of that launch (staged in the rider context ``riders`` the launch is given).  ``finish_flag_draw(riders)`` must
+    follow the launch."""
     scope = _FLAG_SCOPE
-    if not FLAG_RIDER or scope is None or _FLAG_STAGED[0]:
+    if not FLAG_RIDER or scope is None:
         return
     device = torch.device(device)
     k = (device, float(p))
@@ -126,23 +126,21 @@ def stage_flag_draw(p, device, rows):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if _FLAG_STATE.get(idx) is None:
         return                        # (the first draw on a device sets the generator state up: the ordinary way)
-    scope.bufs[k] = [draw_flags(want, p, device, stage=True), 0, 0]
-    _FLAG_STAGED[0] = True
+    scope.bufs[k] = [draw_flags(want, p, device, riders=riders), 0, 0]
 
 
-def finish_flag_draw():
-    """Behind that launch: a staged draw the launch did not take (another kernel form) is launched now."""
-    if _FLAG_STAGED[0]:
-        _FLAG_STAGED[0] = False
-        _hip.check(_hip.lib().mmdfn_keep_flags_flush(_hip.stream()), "mmdfn_keep_flags_flush")
+def finish_flag_draw(riders):
+    """Behind that launch: a draw staged in ``riders`` that the launch did not take (another kernel form) is launched now."""
+    _hip.check(_hip.lib().mmdfn_keep_flags_flush(riders, _hip.stream()), "mmdfn_keep_flags_flush")
 
 
-def draw_flags(n, p, device, stage=False):
+def draw_flags(n, p, device, riders=None):
     """n (a multiple of 4) fresh fp32 keep flags from the package's Philox kernel (csrc/encoder_glue.hip).  The generator state
     lives on the device and every launch advances it, so replays of a captured graph draw new flags.  In eager mode the state
     follows torch's CUDA generator: it is re-seeded from (initial_seed, offset) whenever those differ from what this function
     left behind (torch.manual_seed, a restored RNG state, other random ops in between), and the generator's offset is advanced
-    by the counters consumed -- `torch.manual_seed(s)` reproduces a run exactly as it does for torch's own dropout."""
+    by the counters consumed -- `torch.manual_seed(s)` reproduces a run exactly as it does for torch's own dropout.
+    ``riders``: a rider context to stage the draw in for the GRU forward launch given it (``stage_flag_draw``)."""
     device = torch.device(device)
     idx = device.index if device.index is not None else torch.cuda.current_device()
     ent = _FLAG_STATE.get(idx)
@@ -163,8 +161,12 @@ def draw_flags(n, p, device, stage=False):
         ent[1] = (now[0], int(gen.get_offset()))
     _FLAG_CONSUMED[idx] = _FLAG_CONSUMED.get(idx, 0) + 4 * ((n8 + 3) // 4)
     out = torch.empty(n, dtype=torch.float32, device=device)
-    fn = _hip.lib().mmdfn_keep_flags_stage if stage else _hip.lib().mmdfn_keep_flags
-    _hip.check(fn(_hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), _hip.stream()), "mmdfn_keep_flags")
+    lib = _hip.lib()
+    if riders is None:
+        rc = lib.mmdfn_keep_flags(_hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), _hip.stream())
+    else:
+        rc = lib.mmdfn_keep_flags_stage(_hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), riders, _hip.stream())
+    _hip.check(rc, "mmdfn_keep_flags")
     return out
 
 

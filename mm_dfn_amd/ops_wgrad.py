@@ -108,7 +108,11 @@ def gemm_tn_grouped(problems):
 # The queue belongs to one backward pass: entering the outermost scope drops anything a failed backward left behind, and
 # leaving it flushes what the engine callback did not (or clears the queue when the backward raised).
 # ---------------------------------------------------------------------------------------------------
-_WGQ = {"segs": [], "outs": {}, "ext": [], "armed": False, "scope": 0, "side": None, "held": [], "pending_join": False}
+# "riders": the backward pass's rider context (_hip.riders_context(), from entering the outermost scope to leaving it) -- every
+# weight-gradient batch launched inside the scope is given it, so that the slab reductions of rider batches waiting there join
+# (or, sharing a destination, go before) the next reduction launch.
+_WGQ = {"segs": [], "outs": {}, "ext": [], "armed": False, "scope": 0, "side": None, "held": [], "pending_join": False,
+        "riders": None, "rider_keep": None, "rider_held": []}
 # MMDFN_EARLY_WGRAD=1: issue the graph-side weight gradients (GCN stack, LSTM gate) on a second stream as soon as the graph
 # part of the backward pass is done, concurrently with the GRU backward recurrence.  OFF by default: measured slower at
 # cfg2 (1.133 vs 1.107 ms per step; the split batches cost 47.6 + 111.5 us against 140.3 us for one, and the concurrent
@@ -134,8 +138,7 @@ class wgrad_batch:
             _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False        # stale entries of a backward that raised
         if _WGQ["scope"] == 0:
             drop_grad_addends()                                             # (same: its callback never ran)
-            if _WGQ.get("rider_keep") or _WGQ.get("rider_held"):            # (a backward that raised with riders under way)
-                _drain_riders(discard=True)
+            _WGQ["riders"], _WGQ["rider_keep"], _WGQ["rider_held"] = _hip.riders_context(), None, []
         _WGQ["scope"] += 1
         return self
 
@@ -150,6 +153,7 @@ class wgrad_batch:
                 _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False    # the callback never ran: drop the half-built batch
                 drop_grad_addends()
                 _drain_riders(discard=True)
+            _WGQ["riders"] = None
             _join_side()
         return False
 
@@ -261,12 +265,14 @@ def stage_riders(rows, T):
     """In front of the plain GRU backward recurrence launch of groups with ``rows`` sequences and ``T`` steps: weight gradients
     queued so far are staged as riders of that launch -- if it is of the kind that takes riders, as many (in queue order, at
     most 16 segments) as the CUs it leaves idle can finish while it runs; the rest stays queued for the next launch / the
-    end-of-backward flush.  ``finish_riders()`` must follow the launch."""
-    if not (RIDERS and _WGQ["scope"] > 0 and _WGQ["outs"]) or _WGQ.get("rider_keep"):
-        return
+    end-of-backward flush.  Returns the rider context to give that launch (None outside a ``wgrad_batch`` scope);
+    ``finish_riders()`` must follow the launch."""
+    riders = _WGQ["riders"]
+    if not (RIDERS and _WGQ["scope"] > 0 and _WGQ["outs"]) or _WGQ["rider_keep"]:
+        return riders
     idle = _hip.lib().mmdfn_gru_seq_bwd_idle_cus(len(rows), _hip.int_array(rows))
     if idle <= 0:
-        return
+        return riders
     step_s = 1e-9 * _hip.lib().mmdfn_gru_seq_bwd_step_ns(len(rows), _hip.int_array(rows))     # (0.75 us; the MFMA form 2.3)
     budget = RIDER_BUDGET * idle * max(T) * step_s * _RIDER_FLOPS_PER_CU_S
     take, nseg, work = [], 0, 0.0
@@ -281,29 +287,29 @@ def stage_riders(rows, T):
         RIDER_LOG.append(dict(idle=idle, T=max(T), budget_gflop=budget / 1e9, taken_gflop=work / 1e9, taken_segments=nseg,
                               queued=[(o["M"], o["N"], len(o["segs"]), sum(a.shape[0] for a, _, _ in o["segs"]), k in take)
                                       for k, o in _WGQ["outs"].items()]))
-    if not take:
-        return
-    outs = [_WGQ["outs"].pop(k) for k in take]      # 'armed' stays set: the end-of-backward callback flushes the rest
-    _flush_outs(outs, None, (), stage=True)
+    if take:
+        outs = [_WGQ["outs"].pop(k) for k in take]      # 'armed' stays set: the end-of-backward callback flushes the rest
+        _flush_outs(outs, None, (), stage=True)
+    return riders
 
 
 def finish_riders():
     """Behind the GRU backward launch: a staged batch the launch did not take (another kernel form) is issued now; the
     references that kept its operands and slabs alive are dropped (the launches are in the stream)."""
-    if _WGQ.get("rider_keep"):
-        rc = _hip.lib().mmdfn_wgrad_riders_flush(_hip.stream())
+    if _WGQ["rider_keep"]:
+        rc = _hip.lib().mmdfn_wgrad_riders_flush(_WGQ["riders"], _hip.stream())
         # the slabs are read again by the reduction launch that takes them in (the end-of-backward batch's): held until then
-        _WGQ.setdefault("rider_held", []).append(_WGQ["rider_keep"])
+        _WGQ["rider_held"].append(_WGQ["rider_keep"])
         _WGQ["rider_keep"] = None
         _hip.check(rc, "mmdfn_wgrad_riders_flush")
 
 
 def _drain_riders(discard=False):
     """End of the backward pass: the rider batches' slab stacks that no reduction launch took in are reduced now."""
-    if _WGQ.get("rider_held") or _WGQ.get("rider_keep"):
-        if _WGQ.get("rider_keep") and not discard:
+    if _WGQ["rider_held"] or _WGQ["rider_keep"]:
+        if _WGQ["rider_keep"] and not discard:
             finish_riders()
-        rc = _hip.lib().mmdfn_wgrad_riders_drain(_hip.stream(), 1 if discard else 0)
+        rc = _hip.lib().mmdfn_wgrad_riders_drain(_WGQ["riders"], _hip.stream(), 1 if discard else 0)
         _WGQ["rider_held"], _WGQ["rider_keep"] = [], None
         _hip.check(rc, "mmdfn_wgrad_riders_drain")
 
@@ -409,8 +415,9 @@ def _ext_destinations(ext):
 
 def _flush_outs(outs, side, ext=(), stage=False):
     ext_items = _ext_destinations(ext) if ext else []
+    riders = _WGQ["riders"]
     if not outs:
-        _prepare_wgrad_batch([], ext_items)(_hip.stream())
+        _prepare_wgrad_batch([], ext_items, riders=riders)(_hip.stream())
         return
     dev = outs[0]["weight"].device
     # gradient destinations: fresh buffers handed to .grad (the usual case: backward runs with .grad = None), or the
@@ -471,12 +478,13 @@ def _flush_outs(outs, side, ext=(), stage=False):
     # foreign slab stacks ride on the last batch's reduction launch (a launch of their own when it has no room left, or when
     # the batch leaves on the side stream)
     ride = bool(ext_items) and side is None and len(batches[-1]) + len(ext_items) <= _WG_MAX
-    prepared = [_prepare_wgrad_batch(b, ext_items if (ride and b is batches[-1]) else None, stage=stage and b is batches[-1])
+    prepared = [_prepare_wgrad_batch(b, ext_items if (ride and b is batches[-1]) else None, stage=stage and b is batches[-1],
+                                     riders=riders)
                 for b in batches]          # allocations (workspace) on the current stream
     if stage:
         _WGQ["rider_keep"] = (outs, prepared)
     if ext_items and not ride:
-        _prepare_wgrad_batch([], ext_items)(_hip.stream())
+        _prepare_wgrad_batch([], ext_items, riders=riders)(_hip.stream())
     if side is not None:
         side.wait_stream(torch.cuda.current_stream())             # operands, zero fills and allocations are ordered before
         _WGQ["held"].append((outs, prepared))
@@ -487,10 +495,12 @@ def _flush_outs(outs, side, ext=(), stage=False):
 
 
 def _launch_wgrad_batch(batch):
-    _prepare_wgrad_batch(batch)(_hip.stream())
+    _prepare_wgrad_batch(batch, riders=_WGQ["riders"])(_hip.stream())
 
 
-def _prepare_wgrad_batch(batch, ext_items=None, stage=False):
+def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
+    """The launch (a function of the stream) of one weight-gradient batch; ``riders``: the rider context of the backward pass
+    (``stage``: the batch is staged in it for the next GRU backward launch)."""
     lib = _hip.lib()
     ia = _hip.int_array
     pa = lambda ts: (ctypes.c_void_p * max(1, len(ts)))(*[None if t is None else t.data_ptr() for t in ts])
@@ -512,7 +522,7 @@ def _prepare_wgrad_batch(batch, ext_items=None, stage=False):
 
         def call_ext(stream, _keep=ext_keep):
             rc = lib.mmdfn_gemm_tn_batch_ext(0, None, None, None, None, None, None, None, 0, None, None, None, None, None, None,
-                                             None, None, *ext_args, stream)
+                                             None, None, *ext_args, riders, stream)
             _hip.check(rc, "mmdfn_gemm_tn_batch_ext")
         return call_ext
     A, B, R, lda, ldb, sh, oi = [], [], [], [], [], [], []
@@ -535,12 +545,12 @@ def _prepare_wgrad_batch(batch, ext_items=None, stage=False):
     def call(stream, _keep=(A, B, C, cs1, cs2, ws, ext_items)):
         if ext_args is not None:
             rc = lib.mmdfn_gemm_tn_batch_ext(len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
-                                             pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), *ext_args, stream)
+                                             pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), *ext_args, riders, stream)
             _hip.check(rc, "mmdfn_gemm_tn_batch_ext")
             return
         fn = lib.mmdfn_wgrad_riders_stage if stage else lib.mmdfn_gemm_tn_batch
         rc = fn(len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
-                pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), stream)
+                pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), riders, stream)
         _hip.check(rc, "mmdfn_wgrad_riders_stage" if stage else "mmdfn_gemm_tn_batch")
     return call
 

@@ -44,6 +44,33 @@ def test_arg_counts_match_header():
         assert n == len(_hip.SIGNATURES[name]), name
 
 
+def test_library_keeps_no_writable_state_of_its_own():
+    """The C ABI is re-entrant: the production library defines no writable data symbol (nm class b / B / d / D) beyond the
+    toolchain's own (reserved names: __hip_* code-object registration, _DYNAMIC, ...), the kernel handles (demangled names end
+    in ')') and the per-kernel attribute memo of mmdfn_allow_big_lds."""
+    import shutil
+    import subprocess
+    from mm_dfn_amd import build
+    if not os.path.exists(build.LIBPATH):
+        pytest.skip("libmmdfn_hip.so not built here (hipcc unavailable?)")
+    nm = "/opt/rocm/llvm/bin/llvm-nm"
+    if not os.path.exists(nm):
+        nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm here")
+    out = subprocess.run([nm, "-C", "--defined-only", build.LIBPATH], check=True, capture_output=True, text=True).stdout
+    state = []
+    for line in out.splitlines():
+        parts = line.split(None, 2)
+        if len(parts) < 3 or parts[1] not in "bBdD":
+            continue
+        name = parts[2]
+        if re.match(r"_[_A-Z]|DW\.ref\.", name) or name.endswith(")") or name.startswith("mmdfn_allow_big_lds<"):
+            continue
+        state.append(name)
+    assert not state, "writable host state in %s: %s" % (os.path.basename(build.LIBPATH), state)
+
+
 def test_cpu_tensors_fail_loudly():
     import torch
     from mm_dfn_amd import ops, _hip

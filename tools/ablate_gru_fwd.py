@@ -19,7 +19,7 @@ lib = _hip.lib()
 
 def run():
     rc = lib.mmdfn_gru_seq_fwd(2, _hip.ptr_array(gi), _hip.ptr_array(whh), _hip.ptr_array(bhh), _hip.ptr_array(ys),
-                               _hip.ptr_array(gates), _hip.int_array([16, 64]), _hip.int_array([110, 110]), H, _hip.stream())
+                               _hip.ptr_array(gates), _hip.int_array([16, 64]), _hip.int_array([110, 110]), H, None, _hip.stream())
     assert rc == 0
 
 

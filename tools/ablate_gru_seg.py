@@ -15,7 +15,7 @@ if len(sys.argv) > 1:
         lib.mmdfn_gru_seq_fwd_seg(1, pa([gi]), pa(whh), pa(bhh), pa([y]), pa([g]), _hip.int_array([rows]), _hip.int_array([T]), H,
                                   pa([None]), _hip.int_array([1]), _hip.int_array([1]), _hip.int_array([-1]), pa([None]), _hip.stream())
     def p():
-        lib.mmdfn_gru_seq_fwd(1, pa([gi]), pa(whh), pa(bhh), pa([y]), pa([g]), _hip.int_array([rows]), _hip.int_array([T]), H, _hip.stream())
+        lib.mmdfn_gru_seq_fwd(1, pa([gi]), pa(whh), pa(bhh), pa([y]), pa([g]), _hip.int_array([rows]), _hip.int_array([T]), H, None, _hip.stream())
     for name, fn in (("plain", p), ("seg", f)):
         for _ in range(10): fn()
         torch.cuda.synchronize()

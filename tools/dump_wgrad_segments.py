@@ -27,11 +27,11 @@ from mm_dfn_amd import ops_wgrad
 orig = ops_wgrad._prepare_wgrad_batch
 
 
-def spy(batch):
+def spy(batch, *args, **kw):
     for (o, Ct, cs, a, segs) in batch:
         for (At, Bt, s_) in segs:
             seen.append((At.shape[0], o["M"], o["N"], s_, At.stride(0), Bt.stride(0), len(cs)))
-    return orig(batch)
+    return orig(batch, *args, **kw)
 
 
 ops_wgrad._prepare_wgrad_batch = spy

@@ -19,10 +19,10 @@ def run(T, rows, iters=30):
     lib = _hip.lib()
 
     def f():
-        lib.mmdfn_gru_seq_fwd(1, _hip.ptr_array([gi]), _hip.ptr_array(whh), _hip.ptr_array(bhh), _hip.ptr_array([y]), _hip.ptr_array([g]), _hip.int_array([rows]), _hip.int_array([T]), H, _hip.stream())
+        lib.mmdfn_gru_seq_fwd(1, _hip.ptr_array([gi]), _hip.ptr_array(whh), _hip.ptr_array(bhh), _hip.ptr_array([y]), _hip.ptr_array([g]), _hip.int_array([rows]), _hip.int_array([T]), H, None, _hip.stream())
 
     def b():
-        lib.mmdfn_gru_seq_bwd(1, _hip.ptr_array([dy]), _hip.ptr_array([y]), _hip.ptr_array([g]), _hip.ptr_array(whh), _hip.ptr_array([dgi]), _hip.ptr_array([dgh]), _hip.int_array([rows]), _hip.int_array([T]), H, _hip.stream())
+        lib.mmdfn_gru_seq_bwd(1, _hip.ptr_array([dy]), _hip.ptr_array([y]), _hip.ptr_array([g]), _hip.ptr_array(whh), _hip.ptr_array([dgi]), _hip.ptr_array([dgh]), _hip.int_array([rows]), _hip.int_array([T]), H, None, _hip.stream())
     out = []
     for fn in (f, b):
         for _ in range(10):

@@ -47,10 +47,10 @@ def case(T, B, P, nm, ctx_rows):
     pa = _hip.ptr_array
 
     def legacy_f():
-        lib.mmdfn_gru_seq_fwd(n, pa(gi), pa(whh), pa(bhh), pa(y), pa(g), R, Ts, H, _hip.stream())
+        lib.mmdfn_gru_seq_fwd(n, pa(gi), pa(whh), pa(bhh), pa(y), pa(g), R, Ts, H, None, _hip.stream())
 
     def legacy_b():
-        lib.mmdfn_gru_seq_bwd(n, pa(dy), pa(y), pa(g), pa(whh), pa(dgi), pa(dgh), R, Ts, H, _hip.stream())
+        lib.mmdfn_gru_seq_bwd(n, pa(dy), pa(y), pa(g), pa(whh), pa(dgi), pa(dgh), R, Ts, H, None, _hip.stream())
 
     def seg(use_rank, tdir):
         rk = pa([None, rank if use_rank else None])
