@@ -46,7 +46,8 @@ extern "C" {
  * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
 int64_t mmdfn_riders_bytes(void);
 
-/* Library / device sanity: returns the ABI version (currently 18: 17 with the rider hand-off made explicit -- the rider context
+/* Library / device sanity: returns the ABI version (currently 19: 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
+ * and the LMF fusion kernels mmdfn_lmf_{fwd,bwd,bwd_width}; 18 = 17 with the rider hand-off made explicit -- the rider context
  * `riders` (mmdfn_riders_bytes) is an argument of mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_keep_flags_{stage,flush},
  * mmdfn_gru_seq_{fwd,bwd} and mmdfn_gemm_tn_batch / _ext; 17 = 16 + the GRU backward launch's weight-gradient riders mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_gru_seq_bwd_idle_cus, mmdfn_gru_seq_bwd_step_ns, and the dropout-flag draw as a rider of the GRU forward launch mmdfn_keep_flags_{stage,flush}, mmdfn_gru_seq_fwd_takes_flags; 16 = 15 + mmdfn_linear_planes_group, mmdfn_party_gather_bwd_colsum, mmdfn_party_combine_bwd_dst, mmdfn_prop_layer_fwd; 15 = 14 + mmdfn_weight_planes_workspace, mmdfn_cut_weight_planes, mmdfn_linear_planes; 14 = 13 + mmdfn_lstm_gate_{planes_workspace,cut_weights,fwd_pre,takes_planes}; 13 = 12 + mmdfn_gemm_tn_batch_ext, mmdfn_head_bwd_partial / _groups, mmdfn_colsum_partial; 12 = 11 + the segmented GRU recurrence mmdfn_gru_seq_{fwd,bwd}_seg, mmdfn_gru_tab_reduce, the strided forms mmdfn_lstm_gate_fwd_ld, mmdfn_gcnii_layer_bwd_ld, mmdfn_focal_loss_{fwd,bwd}_ignore and mmdfn_focal_loss_fwd_grad). */
 int mmdfn_abi_version(void);
@@ -563,6 +564,35 @@ int mmdfn_head_bwd_groups(void);
 int mmdfn_head_bwd_partial(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W, float* dF,
                            float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split, float mscale,
                            void* stream);
+/* The same three launches with the ReLU made optional (ABI 19): relu != 0 is mmdfn_head_fwd / _bwd / _bwd_partial, relu == 0 is
+ * z = F (.) mask * mscale and dF = (g W) (.) mask * mscale -- the head of the graph-free model (reference model.py:1403-1404:
+ * dropout_ -> smax_fc -> log_softmax). */
+int mmdfn_head_fwd_act(const float* F, const float* mask, const float* W, const float* bias, float* logp, int64_t N, int Wd,
+                       int C, int ldf, int split, float mscale, int relu, void* stream);
+int mmdfn_head_bwd_act(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W, float* dF,
+                       float* dW, float* db, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split,
+                       float mscale, int relu, void* stream);
+int mmdfn_head_bwd_partial_act(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W,
+                               float* dF, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split, float mscale,
+                               int relu, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * LMF  low-rank multimodal fusion (reference model_fusion.py:214-310), the pointwise part of each direction (csrc/lmf.hip);
+ * the products [1, h_m] . factor_m run on the grouped linear / gemm_tn kernels.  O = output_dim, R = rank <= 8, modalities
+ * in the order a, v, t.
+ *   fwd: P (N rows, stride ldp >= 3 R O) holds P_m,r = h_m . factor_m[r, 1:, :] in column block m R + r; the kernel adds the
+ *        constant row factor_m[r, 0, :] (at factor_m + r * rank_stride_m) in place and writes
+ *        out = sum_r w[r] P_a,r (.) P_v,r (.) P_t,r + bias   (N, O), row stride ldo.
+ *   bwd: from g = d out (row stride ldg) and the P of the forward, D (row stride ldd >= mmdfn_lmf_bwd_width(O, R)) gets
+ *        [dP (3 R O) | g (O) | T (R) | zeros]: dP_m,r = g w_r times the other two modalities' P_.,r, T_r = sum_o g P_a,r P_v,r P_t,r;
+ *        the column sums of D are d factor_m[r, 0, :], d bias and d w.
+ * ------------------------------------------------------------------------- */
+int mmdfn_lmf_bwd_width(int O, int R);
+int mmdfn_lmf_fwd(float* P, const float* factor_a, const float* factor_v, const float* factor_t, int64_t rank_stride_a,
+                  int64_t rank_stride_v, int64_t rank_stride_t, const float* w, const float* bias, float* out, int64_t N, int O,
+                  int R, int ldp, int ldo, void* stream);
+int mmdfn_lmf_bwd(const float* g, const float* P, const float* w, float* D, int64_t N, int O, int R, int ldg, int ldp, int ldd,
+                  void* stream);
 
 /* ---------------------------------------------------------------------------
  * K10  FocalLoss (reference loss.py:14-34) as one launch each way:

@@ -81,6 +81,12 @@ SIGNATURES = {
     "mmdfn_head_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _P],
     "mmdfn_head_bwd_workspace": [_I, _I],
     "mmdfn_head_bwd": [_P] * 9 + [_L, _I, _I, _I, _I, _I, _F, _P],
+    "mmdfn_head_fwd_act": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _I, _P],
+    "mmdfn_head_bwd_act": [_P] * 9 + [_L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "mmdfn_head_bwd_partial_act": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "mmdfn_lmf_bwd_width": [_I, _I],
+    "mmdfn_lmf_fwd": [_P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "mmdfn_lmf_bwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "mmdfn_focal_loss_fwd": [_P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
     "mmdfn_focal_loss_bwd": [_P, _P, _P, _P, _L, _I, _P],
     "mmdfn_focal_loss_fwd_grad": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -102,7 +108,7 @@ SIGNATURES = {
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class HipLibraryError(RuntimeError):

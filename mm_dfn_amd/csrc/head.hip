@@ -9,6 +9,8 @@
 // products are reduced across the wave; C is far too small for the matrix cores to matter (2 N W C flop = 19 MFLOP at
 // cfg2) -- the kernel is a single pass over F at HBM / L2 speed.
 // Backward:  g = dlogp - exp(logp) * sum_c dlogp_c;   dF = (g W) (.) [z > 0] m mscale;   dW = g^T z;   db = sum_rows g.
+// RELU = false (the _act entry points with relu = 0): z = F (.) m * mscale and dF = (g W) (.) m mscale -- the head of the
+// graph-free model (model.py:1403-1404: dropout_ -> smax_fc -> log_softmax, no ReLU).
 //   dW / db: every wave keeps its partial sums in registers over the rows it owns, waves of a workgroup meet in LDS,
 //   workgroups write partial slabs and a second tiny kernel sums them in a fixed order (bit-reproducible, no atomics).
 #include "mmdfn_internal.h"
@@ -30,6 +32,7 @@ __device__ __forceinline__ int64_t feat_off(int64_t row, int col, int ld, int sp
     return ((int64_t)blk * N + row) * ld + (col - blk * split);
 }
 
+template <bool RELU>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ Fm, const float* __restrict__ mask,
                                                        const float* __restrict__ Wt, const float* __restrict__ bias,
                                                        float* __restrict__ logp, int64_t N, int W, int C, int ldf,
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
                     const float4 m = mv[u];
                     z.x *= m.x * mscale; z.y *= m.y * mscale; z.z *= m.z * mscale; z.w *= m.w * mscale;
                 }
-                z.x = fmaxf(z.x, 0.f); z.y = fmaxf(z.y, 0.f); z.z = fmaxf(z.z, 0.f); z.w = fmaxf(z.w, 0.f);
+                if (RELU) { z.x = fmaxf(z.x, 0.f); z.y = fmaxf(z.y, 0.f); z.z = fmaxf(z.z, 0.f); z.w = fmaxf(z.w, 0.f); }
 #pragma unroll
                 for (int c = 0; c < HC_MAX; ++c) {
                     if (c < C) {
@@ -116,6 +119,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
 }
 
 // grid (HB_GROUPS, column blocks).  part: [groups][C][W] slabs of dW, bpart: [groups][C] slabs of db (column block 0).
+template <bool RELU>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlogp, const float* __restrict__ logp,
                                                        const float* __restrict__ Fm, const float* __restrict__ mask,
                                                        const float* __restrict__ Wt, float* __restrict__ dF,
@@ -194,7 +198,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             float4 z = zc[s];
             float4 m = mc[s];
             if (mask) { m.x *= mscale; m.y *= mscale; m.z *= mscale; m.w *= mscale; }
-            z.x = fmaxf(z.x * m.x, 0.f); z.y = fmaxf(z.y * m.y, 0.f); z.z = fmaxf(z.z * m.z, 0.f); z.w = fmaxf(z.w * m.w, 0.f);
+            z.x *= m.x; z.y *= m.y; z.z *= m.z; z.w *= m.w;
+            if (RELU) { z.x = fmaxf(z.x, 0.f); z.y = fmaxf(z.y, 0.f); z.z = fmaxf(z.z, 0.f); z.w = fmaxf(z.w, 0.f); }
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int c = 0; c < HC_MAX; ++c) {
@@ -204,8 +209,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                     dw[c][s].x += g[c] * z.x; dw[c][s].y += g[c] * z.y; dw[c][s].z += g[c] * z.z; dw[c][s].w += g[c] * z.w;
                 }
             }
-            d.x = z.x > 0.f ? d.x * m.x : 0.f; d.y = z.y > 0.f ? d.y * m.y : 0.f;
-            d.z = z.z > 0.f ? d.z * m.z : 0.f; d.w = z.w > 0.f ? d.w * m.w : 0.f;
+            if (RELU) {
+                d.x = z.x > 0.f ? d.x * m.x : 0.f; d.y = z.y > 0.f ? d.y * m.y : 0.f;
+                d.z = z.z > 0.f ? d.z * m.z : 0.f; d.w = z.w > 0.f ? d.w * m.w : 0.f;
+            } else {
+                d.x *= m.x; d.y *= m.y; d.z *= m.z; d.w *= m.w;
+            }
             *reinterpret_cast<float4*>(dF + feat_off(row, col0 + 4 * j, lddf, split, N)) = d;
         }
     }
@@ -276,23 +285,34 @@ static bool bad_split(int Wd, int ld, int split) {
     return split < 4 || (split & 3) || Wd % split || ld < split || (ld & 3);
 }
 
-extern "C" int mmdfn_head_fwd(const float* F, const float* mask, const float* W, const float* bias, float* logp, int64_t N,
-                              int Wd, int C, int ldf, int split, float mscale, void* stream) {
+static int head_fwd_impl(const float* F, const float* mask, const float* W, const float* bias, float* logp, int64_t N, int Wd,
+                         int C, int ldf, int split, float mscale, bool relu, void* stream) {
     if (N <= 0 || Wd < 4 || (Wd & 3) || C < 1 || C > HC_MAX || bad_split(Wd, ldf, split) || (int64_t)C * Wd * 4 > 150 * 1024) return -1;
     int64_t grid = (N + 3) / 4;
     if (grid > 1024) grid = 1024;
-    if (int e = mmdfn_allow_big_lds(head_fwd_kernel)) return e;
-    hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)grid), dim3(256), (size_t)C * Wd * sizeof(float), (hipStream_t)stream, F, mask,
+    auto kern = relu ? head_fwd_kernel<true> : head_fwd_kernel<false>;
+    if (int e = mmdfn_allow_big_lds(kern)) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), (size_t)C * Wd * sizeof(float), (hipStream_t)stream, F, mask,
                        W, bias, logp, N, Wd, C, ldf, split, mscale);
     MMDFN_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mmdfn_head_fwd(const float* F, const float* mask, const float* W, const float* bias, float* logp, int64_t N,
+                              int Wd, int C, int ldf, int split, float mscale, void* stream) {
+    return head_fwd_impl(F, mask, W, bias, logp, N, Wd, C, ldf, split, mscale, true, stream);
+}
+
+extern "C" int mmdfn_head_fwd_act(const float* F, const float* mask, const float* W, const float* bias, float* logp, int64_t N,
+                                  int Wd, int C, int ldf, int split, float mscale, int relu, void* stream) {
+    return head_fwd_impl(F, mask, W, bias, logp, N, Wd, C, ldf, split, mscale, relu != 0, stream);
 }
 
 extern "C" int64_t mmdfn_head_bwd_workspace(int Wd, int C) { return (int64_t)HB_GROUPS * ((int64_t)C * Wd + C); }
 
 static int head_bwd_impl(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W, float* dF,
                          float* dW, float* db, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split,
-                         float mscale, bool reduce, void* stream) {
+                         float mscale, bool reduce, bool relu, void* stream) {
     if (N <= 0 || Wd < 4 || (Wd & 3) || C < 1 || C > HC_MAX || bad_split(Wd, ldf, split) || bad_split(Wd, lddf, split)) return -1;
     hipStream_t s = (hipStream_t)stream;
     float* part = workspace;
@@ -300,8 +320,9 @@ static int head_bwd_impl(const float* dlogp, const float* logp, const float* F, 
     const int nblk = (Wd + HB_COLS - 1) / HB_COLS;
     const size_t lds = (size_t)4 * C * HB_COLS * sizeof(float);       // wave partials (>= the C x HB_COLS weight block)
     if (lds > 150 * 1024) return -1;
-    if (int e = mmdfn_allow_big_lds(head_bwd_kernel)) return e;
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(HB_GROUPS, nblk), dim3(256), lds, s, dlogp, logp, F, mask, W, dF, part, bpart, N, Wd, C,
+    auto kern = relu ? head_bwd_kernel<true> : head_bwd_kernel<false>;
+    if (int e = mmdfn_allow_big_lds(kern)) return e;
+    hipLaunchKernelGGL(kern, dim3(HB_GROUPS, nblk), dim3(256), lds, s, dlogp, logp, F, mask, W, dF, part, bpart, N, Wd, C,
                        ldf, lddf, split, mscale);
     MMDFN_CHECK_LAUNCH();
     if (!reduce) return 0;
@@ -314,7 +335,14 @@ static int head_bwd_impl(const float* dlogp, const float* logp, const float* F, 
 extern "C" int mmdfn_head_bwd(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W, float* dF,
                               float* dW, float* db, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split,
                               float mscale, void* stream) {
-    return head_bwd_impl(dlogp, logp, F, mask, W, dF, dW, db, workspace, N, Wd, C, ldf, lddf, split, mscale, true, stream);
+    return head_bwd_impl(dlogp, logp, F, mask, W, dF, dW, db, workspace, N, Wd, C, ldf, lddf, split, mscale, true, true, stream);
+}
+
+extern "C" int mmdfn_head_bwd_act(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W,
+                                  float* dF, float* dW, float* db, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf,
+                                  int split, float mscale, int relu, void* stream) {
+    return head_bwd_impl(dlogp, logp, F, mask, W, dF, dW, db, workspace, N, Wd, C, ldf, lddf, split, mscale, true, relu != 0,
+                         stream);
 }
 
 // The same launch without the slab reduction: workspace then holds mmdfn_head_bwd_groups() slabs of dW ([groups][C][Wd]) followed
@@ -323,5 +351,13 @@ extern "C" int mmdfn_head_bwd_groups(void) { return HB_GROUPS; }
 extern "C" int mmdfn_head_bwd_partial(const float* dlogp, const float* logp, const float* F, const float* mask, const float* W,
                                       float* dF, float* workspace, int64_t N, int Wd, int C, int ldf, int lddf, int split,
                                       float mscale, void* stream) {
-    return head_bwd_impl(dlogp, logp, F, mask, W, dF, nullptr, nullptr, workspace, N, Wd, C, ldf, lddf, split, mscale, false, stream);
+    return head_bwd_impl(dlogp, logp, F, mask, W, dF, nullptr, nullptr, workspace, N, Wd, C, ldf, lddf, split, mscale, false, true,
+                         stream);
+}
+
+extern "C" int mmdfn_head_bwd_partial_act(const float* dlogp, const float* logp, const float* F, const float* mask,
+                                          const float* W, float* dF, float* workspace, int64_t N, int Wd, int C, int ldf,
+                                          int lddf, int split, float mscale, int relu, void* stream) {
+    return head_bwd_impl(dlogp, logp, F, mask, W, dF, nullptr, nullptr, workspace, N, Wd, C, ldf, lddf, split, mscale, false,
+                         relu != 0, stream);
 }

@@ -3,8 +3,10 @@
 Same constructor and ``forward(U, qmask, umask, seq_lengths, U_a, U_v,
 test_label)`` signature and the same 86 ``state_dict`` keys as the reference,
 restricted to the configuration MM-DFN trains (base_model='LSTM',
-multi_modal=True, graph_type='GDF', use_crn_speaker=True).  Other ablation
-branches of the reference constructor raise NotImplementedError.
+multi_modal=True, graph_type='GDF', use_crn_speaker=True), the unimodal-graph
+sibling 'DeepGCN' and the graph-free baselines (graph_type='None' with the
+post-hoc fusions concat_subsequently, gated, mfn_only, lmf_only, concat_only).
+Other ablation branches of the reference constructor raise NotImplementedError.
 
 Host-side structure differs from the reference on purpose (MI355X-first):
   * the B*P*2*3 Python slice-assign loops of the speaker-party encoder
@@ -22,7 +24,7 @@ import torch.nn.functional as F
 
 from . import gru as fused_gru
 from . import ops
-from .fusion import MFN, MMGatedAttention
+from .fusion import LMF, MFN, MMGatedAttention
 from .graph_conv import GCNII
 from .layout import IndexScope, PinnedLRU
 from .mm_gcn import MM_GCN
@@ -106,18 +108,32 @@ class DialogueGNNModel(nn.Module):
                  dataset='IEMOCAP', use_speaker=True, use_modal=False, reason_flag=False, multi_modal=True,
                  use_crn_speaker=False, speaker_weights='1-1-1', modal_weight=1.0):
         super().__init__()
-        if base_model != 'LSTM' or not multi_modal or graph_type not in ('GDF', 'DeepGCN'):
-            raise NotImplementedError("mm_dfn_amd implements the MM-DFN hot path (graph_type='GDF') and its unimodal-graph "
-                                      "sibling 'DeepGCN' only, with base_model='LSTM', multi_modal=True (got %r, %r, %r)"
-                                      % (base_model, multi_modal, graph_type))
+        if base_model != 'LSTM' or not multi_modal or graph_type not in ('GDF', 'DeepGCN', 'None'):
+            raise NotImplementedError("mm_dfn_amd implements the MM-DFN hot path (graph_type='GDF'), its unimodal-graph "
+                                      "sibling 'DeepGCN' and the graph-free baselines 'None' only, with base_model='LSTM', "
+                                      "multi_modal=True (got %r, %r, %r)" % (base_model, multi_modal, graph_type))
         if graph_type == 'GDF' and att_type not in ('concat_subsequently', 'mfn'):
             raise NotImplementedError("att_type must be 'concat_subsequently' (the MM-DFN scripts) or 'mfn'")
-        if graph_type == 'DeepGCN' and att_type not in ('concat_subsequently', 'gated'):
-            raise NotImplementedError("DeepGCN: att_type must be 'concat_subsequently' or 'gated'")
+        if graph_type == 'DeepGCN' and att_type not in ('concat_subsequently', 'gated', 'mfn'):
+            raise NotImplementedError("DeepGCN: att_type must be 'concat_subsequently', 'gated' or 'mfn'")
+        if graph_type == 'None':
+            if att_type == 'tfn_only':
+                raise NotImplementedError("graph_type='None' with att_type='tfn_only': the tensor-fusion kernels are not built")
+            if att_type not in ('concat_subsequently', 'gated', 'mfn_only', 'lmf_only', 'concat_only'):
+                raise NotImplementedError("graph_type='None': att_type must be one of concat_subsequently, gated, mfn_only, "
+                                          "lmf_only, concat_only (model.py:1386-1400), got %r" % (att_type,))
+            if graph_hidden_size != 100:
+                raise NotImplementedError("graph_type='None': the reference's fusion widths are fixed (300 per modality, "
+                                          "model.py:985-1005), so graph_hidden_size must be 100, got %r" % (graph_hidden_size,))
+            if att_type == 'concat_subsequently' and not use_residue:
+                raise NotImplementedError("graph_type='None', concat_subsequently, use_residue=False: the reference's smax_fc "
+                                          "(100 per modality, model.py:985) does not match its 300-wide features")
         present = [m for m in 'avl' if m in modals]
         if sorted(modals) != sorted(present) or len(present) < 2:
             raise NotImplementedError("modals must name two or three of 'a', 'v', 'l' (model_mm.py:97-106), got %r" % (modals,))
-        if len(present) < 3 and (graph_type != 'GDF' or att_type != 'concat_subsequently'):
+        if len(present) < 3 and graph_type == 'None' and att_type not in ('concat_subsequently', 'gated'):
+            raise NotImplementedError("graph_type='None' with %r fuses all three modalities (model.py:1366,1389-1398)" % att_type)
+        if len(present) < 3 and graph_type != 'None' and (graph_type != 'GDF' or att_type != 'concat_subsequently'):
             raise NotImplementedError("two-modality graphs: graph_type='GDF' with att_type='concat_subsequently' only")
         if 2 * D_e != 200:
             raise NotImplementedError("the reference hard-codes a 200-wide encoder (model.py:847-849,1074); D_e must be 100")
@@ -169,6 +185,10 @@ class DialogueGNNModel(nn.Module):
                                dropout=dropout, lamda=0.5, alpha=0.1, variant=True, return_feature=True,
                                use_residue=use_residue, reason_flag=reason_flag)
             self.graph_net_a, self.graph_net_v, self.graph_net_l = mk(), mk(), mk()
+        elif graph_type == 'None':
+            # model.py:960-970: one Linear(200, graph_hidden_size) per modality present, its output put before the features
+            for m in present:
+                setattr(self, "graph_net_" + m, nn.Linear(hidden, graph_hidden_size))
         else:
             self.graph_model = MM_GCN(a_dim=hidden, v_dim=hidden, l_dim=hidden, n_dim=hidden, nlayers=Deep_GCN_nlayers,
                                       nhidden=graph_hidden_size, nclass=n_classes, dropout=dropout, lamda=lamda,
@@ -177,11 +197,17 @@ class DialogueGNNModel(nn.Module):
                                       use_modal=use_modal, reason_flag=reason_flag, modal_weight=modal_weight)
         self.gatedatt = MMGatedAttention(hidden + graph_hidden_size, graph_hidden_size, att_type='general')
         self.dropout_ = nn.Dropout(dropout)
-        if att_type == 'mfn':
+        if att_type in ('mfn', 'mfn_only'):
             self.mfn = MFN()                                      # model.py:991-994
             self.smax_fc = nn.Linear(400, n_classes)
+        elif att_type == 'lmf_only':
+            self.lmf = LMF()                                      # model.py:1000-1003
+            self.smax_fc = nn.Linear(300, n_classes)
+        elif att_type == 'concat_only':
+            self.smax_fc = nn.Linear(900, n_classes)              # model.py:1004-1005
         elif att_type == 'gated':
-            self.smax_fc = nn.Linear(100 * len(self.modals), n_classes)   # model.py:985-989 (three modalities)
+            # model.py:985-989
+            self.smax_fc = nn.Linear(100 * len(self.modals) if len(self.modals) == 3 else 100, n_classes)
         else:
             width = (hidden + graph_hidden_size) if use_residue else graph_hidden_size
             self.smax_fc = nn.Linear(width * len(self.modals), n_classes)
@@ -286,14 +312,21 @@ class DialogueGNNModel(nn.Module):
             raise ValueError("modals=%r needs %s" % (''.join(self.present), "U_a and U_v" if len(self.present) == 3 else
                                                      "U_a" if 'a' in self.present and U_a is None else "U_v"))
         feats = self.encode(U, qmask, seq_lengths, U_a, U_v)
+        if self.graph_type == 'None':
+            return self._forward_graph_free(feats, U, seq_lengths), None, None, None, None
         if self.graph_type == 'DeepGCN':
             # model.py:1242-1290: three independent unimodal graphs, fused after the graph stage;
             # NB dropout THEN ReLU on the fused features, as in the GDF head
             ea = self.graph_net_a(feats[0], seq_lengths, qmask)
             ev = self.graph_net_v(feats[1], seq_lengths, qmask)
             el = self.graph_net_l(feats[2], seq_lengths, qmask)
-            fused = (self.gatedatt(ea, ev, el, self.modals) if self.att_type == 'gated'
-                     else torch.cat([ea, ev, el], dim=-1))
+            if self.att_type == 'mfn':
+                # model.py:1263-1293: l, a, v through the memory fusion network over time
+                fused = self._mfn_over_time(torch.cat([el, ea, ev], dim=-1), U, seq_lengths)
+            elif self.att_type == 'gated':
+                fused = self.gatedatt(ea, ev, el, self.modals)
+            else:
+                fused = torch.cat([ea, ev, el], dim=-1)
             return ops.head(fused, self.smax_fc.weight, self.smax_fc.bias, self.dropout_.p, self.training), None, None, None, None
         # without the memory-fusion stage the head reads the (M, N, 300) graph output in place (stacked_out): the
         # cat([a, v, l], -1) of model_mm.py:113-117 and its backward are never materialised
@@ -314,11 +347,7 @@ class DialogueGNNModel(nn.Module):
             os.makedirs(out_dir, exist_ok=True)
             np.save(os.path.join(out_dir, "1080_v2_test_output_multi_{}".format(index)), dump.detach().cpu().numpy())
         if self.att_type == 'mfn':
-            # re-pad (N, 900) -> (L, B, 900), memory fusion over time, strip again (model.py:1303-1326)
-            L, B = U.shape[0], U.shape[1]
-            idx = _flat_index([int(x) for x in seq_lengths], L, B, fused.device)
-            padded = fused.new_zeros(L * B, fused.shape[1]).index_copy(0, idx, fused).view(L, B, -1)
-            fused = self.mfn(padded).reshape(L * B, -1).index_select(0, idx)
+            fused = self._mfn_over_time(fused, U, seq_lengths)
         if test_label:
             # model.py:1331-1335: the class scores behind smax_fc are dumped as well, so the head runs stage by stage here
             import os
@@ -333,3 +362,26 @@ class DialogueGNNModel(nn.Module):
         # dropout -> ReLU -> smax_fc -> log_softmax (model.py:1328-1337) as one fused launch each way
         log_prob = ops.head(fused, self.smax_fc.weight, self.smax_fc.bias, self.dropout_.p, self.training)
         return log_prob, None, None, None, None
+
+    def _mfn_over_time(self, fused, U, seq_lengths):
+        """re-pad (N, 900) -> (L, B, 900), memory fusion over time, strip again (model.py:1303-1326, 1263-1293, 1365-1386)."""
+        L, B = U.shape[0], U.shape[1]
+        idx = _flat_index([int(x) for x in seq_lengths], L, B, fused.device)
+        padded = fused.new_zeros(L * B, fused.shape[1]).index_copy(0, idx, fused).view(L, B, -1)
+        return self.mfn(padded).reshape(L * B, -1).index_select(0, idx)
+
+    def _forward_graph_free(self, feats, U, seq_lengths):
+        """graph_type='None' (model.py:1374-1404): E_m = [graph_net_m(f_m) | f_m] for every modality in one grouped launch
+        ((M, N, 300), order a, v, l), the post-hoc fusion, then dropout_ -> smax_fc -> log_softmax without a ReLU."""
+        nets = [getattr(self, "graph_net_" + m) for m in self.present]
+        E = ops.residual_products(feats, [n.weight for n in nets], [n.bias for n in nets])
+        by = dict(zip(self.present, (E[i] for i in range(len(self.present)))))
+        if self.att_type in ('concat_subsequently', 'concat_only'):
+            fused = E                    # read in place by the head as cat([E_a, E_v, E_l], -1)
+        elif self.att_type == 'gated':
+            fused = self.gatedatt(by.get('a', []), by.get('v', []), by.get('l', []), self.modals)
+        elif self.att_type == 'mfn_only':
+            fused = self._mfn_over_time(torch.cat([by['l'], by['a'], by['v']], dim=-1), U, seq_lengths)
+        else:
+            fused = self.lmf(by['a'], by['v'], by['l'])
+        return ops.head(fused, self.smax_fc.weight, self.smax_fc.bias, self.dropout_.p, self.training, relu=False)

@@ -10,10 +10,15 @@
 * ``MMGatedAttention`` ('general', model.py:718-781): unreachable under graph_type='GDF' in the reference
   (shape bug); provided at module level, with the reference's state_dict keys: one grouped launch
   for the three transforms, one fused kernel per modality pair (gate dot product, sigmoid, tanh, blend) each way.
+* ``LMF`` (model_fusion.py:214-310): low-rank multimodal fusion, the ``lmf_only`` option of the graph-free model
+  (model.py:1394-1395).  The three subnets are one grouped launch, the 3 R products [1, h_m] . factor_m grouped launches into
+  column blocks of one buffer, and the rank-weighted product over modalities one fused kernel each way (csrc/lmf.hip).
+  As in the reference, ``post_fusion_dropout`` is constructed and never applied.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.nn.init import xavier_normal_
 
 from . import ops
 
@@ -120,3 +125,34 @@ class MMGatedAttention(nn.Module):
         if len(out) == 1:
             return out[0]
         return torch.cat(out, -1)
+
+
+class LMF(nn.Module):
+    def __init__(self, input_dims=(300, 300, 300), hidden_dims=(300, 300, 300), dropouts=0.4, output_dim=300, rank=4,
+                 use_softmax=False):
+        super().__init__()
+        if use_softmax:
+            raise NotImplementedError("LMF(use_softmax=True) is not constructed by the reference model (model.py:1001-1003)")
+        self.audio_in, self.video_in, self.text_in = input_dims
+        self.audio_hidden, self.video_hidden, self.text_hidden = hidden_dims
+        self.audio_subnet = nn.Linear(self.audio_in, self.audio_hidden)
+        self.video_subnet = nn.Linear(self.video_in, self.video_hidden)
+        self.text_subnet = nn.Linear(self.text_in, self.text_hidden)
+        self.output_dim = output_dim
+        self.rank = rank
+        self.use_softmax = use_softmax
+        self.post_fusion_dropout = nn.Dropout(p=dropouts)
+        self.audio_factor = nn.Parameter(torch.empty(rank, self.audio_hidden + 1, output_dim))
+        self.video_factor = nn.Parameter(torch.empty(rank, self.video_hidden + 1, output_dim))
+        self.text_factor = nn.Parameter(torch.empty(rank, self.text_hidden + 1, output_dim))
+        self.fusion_weights = nn.Parameter(torch.empty(1, rank))
+        self.fusion_bias = nn.Parameter(torch.zeros(1, output_dim))
+        for p in (self.audio_factor, self.video_factor, self.text_factor, self.fusion_weights):
+            xavier_normal_(p)
+
+    def forward(self, audio_x, video_x, text_x):
+        """(N, input_dims[m]) each -> (N, output_dim); N = 1 gives (1, output_dim) as the reference's squeeze / view does."""
+        nets = (self.audio_subnet, self.video_subnet, self.text_subnet)
+        ha, hv, ht = ops.linear_group([audio_x, video_x, text_x], [n.weight for n in nets], [n.bias for n in nets], hip=True)
+        return ops.lmf_fuse(ha, hv, ht, self.audio_factor, self.video_factor, self.text_factor, self.fusion_weights,
+                            self.fusion_bias)

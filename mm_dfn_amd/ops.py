@@ -36,7 +36,8 @@ from .ops_party import (  # noqa: F401
     party_combine,
 )
 from .ops_fusion import (  # noqa: F401
-    _SoftmaxScale, softmax_scale, _MfnMem, mfn_mem, _GatedPair, gated_pair,
+    _SoftmaxScale, softmax_scale, _MfnMem, mfn_mem, _GatedPair, gated_pair, _ResidualProducts, residual_products, _Lmf,
+    lmf_fuse,
 )
 from .ops_flags import (  # noqa: F401
     _FLAG_SCOPE, _FLAG_HINT, flag_pool, keep_scale, _FLAG_STATE, _FLAG_CONSUMED, flags_consumed, flag_state_snapshot,
