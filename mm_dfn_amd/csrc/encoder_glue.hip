@@ -189,7 +189,8 @@ __global__ void party_combine_bwd_kernel(const float* __restrict__ dout, const i
 
 // The same gradients written DESTINATION by destination, so that nothing has to be zeroed first (the caller's fill was a launch
 // of its own): workgroup (b, p, row slice) rebuilds the party's time list from `rank`, writes dE[k, (m, b, p), :] = w_m dout[m][n]
-// for k below the party's count and zeros above it; the p = 0 workgroups also write dbase_m[t, b, :] = dout[m][n] or zero (padding).
+// for k below the party's count where p is the last speaker flagged on that utterance, and zeros elsewhere (k at or above the
+// count, a later speaker flagged, a padding row); the p = 0 workgroups also write dbase_m[t, b, :] = dout[m][n] or zero (padding).
 // inv[t * B + b] = n, the row of (t, b) in the stripped order, or -1.
 __global__ __launch_bounds__(256) void party_combine_bwd_dst_kernel(const float* __restrict__ dout, const int32_t* __restrict__ rank,
                                                                     const int64_t* __restrict__ inv, ModPtrsW dbase,
@@ -229,7 +230,13 @@ __global__ __launch_bounds__(256) void party_combine_bwd_dst_kernel(const float*
     int my_e = -1, my_b = -1;
     if (tid < nk) {
         const int k = k_lo + tid;
-        if (k < cnt) my_e = (int)inv[(int64_t)sel[k] * B + b];
+        if (k < cnt) {
+            // the utterance's party term is the LAST flagged speaker's (party_combine_kernel): a later flag means zeros here
+            const int t = sel[k];
+            bool later = false;
+            for (int q = p + 1; q < P && !later; ++q) later = rank[((int64_t)t * B + b) * P + q] >= 0;
+            if (!later) my_e = (int)inv[(int64_t)t * B + b];
+        }
         if (p == 0) my_b = (int)inv[(int64_t)k * B + b];
     }
     __syncthreads();

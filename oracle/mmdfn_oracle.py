@@ -142,7 +142,9 @@ def party_encode(X, qmask, params, dropout=0.0, training=False, engine="manual")
     """For every speaker p: compact that speaker's utterances to the front of
     a zero (L, B, H) buffer, run the shared ``rnn_parties`` BiGRU over the
     full padded length, scatter the first k outputs back to the speaker's
-    positions.  X: (L, B, H), qmask: (L, B, P).  Returns U_p: (L, B, H)."""
+    positions.  X: (L, B, H), qmask: (L, B, P).  Returns U_p: (L, B, H).
+    The scatter ASSIGNS speaker by speaker (model.py:1084-1087): at an
+    utterance flagged for several speakers the last one's encoding wins."""
     L, B, Hd = X.shape
     P = qmask.shape[2]
     Xb = X.transpose(0, 1)            # (B, L, H)
@@ -159,7 +161,7 @@ def party_encode(X, qmask, params, dropout=0.0, training=False, engine="manual")
         for p in range(P):
             k = idx[b][p].numel()
             if k > 0:
-                acc = acc.index_add(0, idx[b][p], enc[p][b][:k])
+                acc = acc.index_copy(0, idx[b][p], enc[p][b][:k])
         out.append(acc)
     return torch.stack(out, 0).transpose(0, 1)
 

@@ -54,6 +54,28 @@ def test_silent_speaker_and_unflagged_utterance():
     assert rel_err(m.rnn_parties.weight_ih_l0.grad, params["rnn_parties.weight_ih_l0"].grad) < 1e-4
 
 
+def test_multi_hot_speaker_rows():
+    """Utterances flagged for several speakers: the reference scatters the party encodings speaker by speaker
+    (model.py:1084-1087), so the last flagged speaker's encoding wins and only that party's GRU rows get its gradient.
+    A backward pass that hands the gradient to every flagged party leaves the log-probs unchanged but moves the gradients:
+    emulated on this batch in float64 (forward: last speaker wins; gradient: every flagged party receives it), it lands
+    0.54 to 1.29 x max away from the oracle on the rnn_parties.* gradients and 0.27 / 0.72 on linear_a / linear_l.weight
+    (linear_v has speaker weight 0: no gap), i.e. over 2 000 x the tolerance below."""
+    cfg = dict(B=2, L=9, P=3, C=6, nlayers=2, D_t=100, D_a=100, D_v=512)
+
+    def edit(q):
+        q[2, 0, :] = 1.0                    # three speakers flagged: speaker 2 wins
+        q[4, 1, :] = 0.0
+        q[4, 1, 0] = q[4, 1, 1] = 1.0       # two speakers flagged: speaker 1 wins
+    m, logp, params, want = _run_model(cfg, [9, 6], 34, edit)
+    assert abs_err(logp, want) < 1e-4
+    keys = [k for k, _ in m.named_parameters() if k.startswith("rnn_parties.")]
+    assert len(keys) == 16
+    named = dict(m.named_parameters())
+    for k in keys + ["linear_a.weight", "linear_v.weight", "linear_l.weight"]:
+        assert rel_err(named[k].grad, params[k].grad) < 1e-4, k
+
+
 @pytest.mark.parametrize("modals", ["av", "al", "vl"])
 @pytest.mark.parametrize("modal_weight", [1.0, 0.6])
 def test_two_modality_graph_module(modals, modal_weight):

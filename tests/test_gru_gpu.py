@@ -132,14 +132,16 @@ def test_matches_torch_gru_module_eval():
     assert abs_err(got, want) < 2e-6
 
 
-@pytest.mark.parametrize("passthrough", [False, True])
+@pytest.mark.parametrize("passthrough,with_inv", [pytest.param(False, False, id="False"), pytest.param(True, False, id="True"),
+                                                 pytest.param(False, True, id="False-inv"), pytest.param(True, True, id="True-inv")])
 @pytest.mark.parametrize("w", [[3.0, 0.0, 1.0], [1.0, 2.0, 0.5], [0.0, 0.0, 2.0]])
 @pytest.mark.parametrize("P,lengths", [(2, [15, 9, 1, 6]), (9, [12, 12, 3]), (3, [1]), (2, [110, 64, 80])])
-def test_party_gather_combine_kernels_match_index_composition(P, lengths, w, passthrough):
+def test_party_gather_combine_kernels_match_index_composition(P, lengths, w, passthrough, with_inv):
     """K3/K4 kernels vs the torch index-op composition of oracle/mmdfn_vectorised.py (itself checked against the oracle
-    on CPU in tests/test_host_logic.py), forward and backward, including a non-one-hot qmask row."""
+    on CPU in tests/test_host_logic.py), forward and backward, including a non-one-hot qmask row.  ``with_inv``: the
+    combine stage's destination-driven backward (what the model runs), else the pre-zeroed one."""
     from mm_dfn_amd import ops
-    from mm_dfn_amd.dialogue_model import _flat_index
+    from mm_dfn_amd.dialogue_model import _flat_index, _flat_inverse
     cfg = dict(B=len(lengths), L=max(lengths), P=P, C=6, nlayers=2, D_t=100, D_a=32, D_v=64)
     m = synthetic.build_model(**cfg)
     b = synthetic.make_batch(4, lengths=lengths, **cfg)
@@ -175,7 +177,8 @@ def test_party_gather_combine_kernels_match_index_composition(P, lengths, w, pas
     else:
         Sk, rank = ops.party_gather([Xk[i] for i in act], q)
     Ek = torch.tanh(Sk * 0.7 + 0.1)
-    outk = ops.party_combine(bases, Ek, rank, idx, w)
+    inv = _flat_inverse(lengths, L, B, DEV) if with_inv else None
+    outk = ops.party_combine(bases, Ek, rank, idx, w, inv=inv)
     (outk * Wg).sum().backward()
     BP = B * P
     for slot, i in enumerate(act):

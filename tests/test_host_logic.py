@@ -10,6 +10,7 @@ import mmdfn_vectorised as V
 from mm_dfn_amd import synthetic, train
 from mm_dfn_amd.dialogue_model import DialogueGNNModel
 from mm_dfn_amd.layout import BlockTileAdjacency, DialogueLayout, pair_list
+from util import party_qmask
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -105,6 +106,31 @@ def test_party_plan_non_one_hot_last_speaker_wins():
             idx = torch.nonzero(q_[0][:, p]).squeeze(-1)
             want[0][idx] = E[p][0][:idx.numel()]
     assert (got.transpose(0, 1) - want).abs().max() < 1e-6
+
+
+def test_oracle_party_encode_last_speaker_wins():
+    """O.party_encode scatters speaker by speaker like the reference (model.py:1084-1087), so at an utterance flagged for
+    several speakers the last one's encoding wins: against the mmdfn_vectorised plan / gather / scatter composition in
+    float64, on a qmask with one-hot, multi-hot (2 and 3 flags), zero-hot and padding-row flags and a silent speaker.  Both
+    sides run the same GRU equations on the same rows; only the batch composition of the GRU products differs, so they
+    agree to float64 rounding.  (With index_add the oracle summed the flagged speakers' encodings at a multi-hot row.)"""
+    lengths, L, P = [9, 6, 4], 9, 4
+    cfg = dict(B=3, L=L, P=P, C=6, nlayers=2, D_t=100, D_a=32, D_v=64)
+    m = synthetic.build_model(**cfg)
+    params = {k: v.double() for k, v in synthetic.seeded_state_dict(m.state_dict(), 13).items()}
+    q = party_qmask(lengths, L, P, 17, pad_flag=True)
+    flags = q.sum(2)
+    valid = torch.arange(L).view(L, 1) < torch.tensor(lengths).view(1, -1)
+    assert bool(((flags == 2) & valid).any()) and bool(((flags == 3) & valid).any())
+    assert bool(((flags == 0) & valid).any()) and bool(((flags > 0) & ~valid).any())
+    assert float(q[:, 2, P - 1].sum()) == 0.0
+    X = torch.from_numpy(np.random.RandomState(18).randn(L, 3, 200))
+    with torch.no_grad():
+        want = O.party_encode(X, q.double(), params, engine="manual")
+        plan = V.party_plan(q)
+        enc = O.bigru2(V.party_gather(X.unsqueeze(0), plan), params, "rnn_parties.", engine="manual")
+        got = V.party_scatter(enc, plan, 1)[0]
+    assert float((got - want).abs().max()) < 1e-12
 
 
 def test_lengths_and_label_flatten():

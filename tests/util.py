@@ -39,6 +39,28 @@ def random_block_adjacency(seed, lengths, M, device):
     return adj, dense, tiles, cross
 
 
+def party_qmask(lengths, L, P, seed, pad_flag=False):
+    """(L, B, P) float32 speaker mask with every row kind the party kernels meet, as far as the shape allows: one-hot rows;
+    in every dialogue of at least 4 utterances one zero-hot valid utterance, one multi-hot row with 2 flags and (3 speakers
+    to choose from) one with 3 flags; speaker P-1 silent in the last dialogue (when P >= 3, or P = 2 with another dialogue
+    left for the multi-hot rows); with ``pad_flag`` one flag on a padding row of every dialogue shorter than L."""
+    rs = np.random.RandomState(seed)
+    B = len(lengths)
+    q = np.zeros((L, B, P), np.float32)
+    silent = (B - 1, P - 1) if P >= 3 or (P == 2 and B >= 2) else None
+    for b, n in enumerate(lengths):
+        spk = [p for p in range(P) if (b, p) != silent]
+        q[np.arange(n), b, rs.choice(spk, size=n)] = 1.0
+        if n >= 4:
+            for t, nf in zip(rs.permutation(n), (0, 2, 3)):
+                if nf <= len(spk):
+                    q[t, b] = 0.0
+                    q[t, b, rs.choice(spk, size=nf, replace=False)] = 1.0
+        if pad_flag and n < L:
+            q[rs.randint(n, L), b, rs.choice(spk)] = 1.0
+    return torch.from_numpy(q)
+
+
 def oracle_params(model):
     return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
 
