@@ -46,7 +46,8 @@ extern "C" {
  * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
 int64_t mmdfn_riders_bytes(void);
 
-/* Library / device sanity: returns the ABI version (currently 19: 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
+/* Library / device sanity: returns the ABI version (currently 20: 19 + mmdfn_linear_planes_group_in (input dropout in the
+ * plane projection's staging step), mmdfn_linear_planes_group_party (party-ordered store) and mmdfn_linear_group_seg2 (two K segments per few-row problem); 19 = 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
  * and the LMF fusion kernels mmdfn_lmf_{fwd,bwd,bwd_width}; 18 = 17 with the rider hand-off made explicit -- the rider context
  * `riders` (mmdfn_riders_bytes) is an argument of mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_keep_flags_{stage,flush},
  * mmdfn_gru_seq_{fwd,bwd} and mmdfn_gemm_tn_batch / _ext; 17 = 16 + the GRU backward launch's weight-gradient riders mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_gru_seq_bwd_idle_cus, mmdfn_gru_seq_bwd_step_ns, and the dropout-flag draw as a rider of the GRU forward launch mmdfn_keep_flags_{stage,flush}, mmdfn_gru_seq_fwd_takes_flags; 16 = 15 + mmdfn_linear_planes_group, mmdfn_party_gather_bwd_colsum, mmdfn_party_combine_bwd_dst, mmdfn_prop_layer_fwd; 15 = 14 + mmdfn_weight_planes_workspace, mmdfn_cut_weight_planes, mmdfn_linear_planes; 14 = 13 + mmdfn_lstm_gate_{planes_workspace,cut_weights,fwd_pre,takes_planes}; 13 = 12 + mmdfn_gemm_tn_batch_ext, mmdfn_head_bwd_partial / _groups, mmdfn_colsum_partial; 12 = 11 + the segmented GRU recurrence mmdfn_gru_seq_{fwd,bwd}_seg, mmdfn_gru_tab_reduce, the strided forms mmdfn_lstm_gate_fwd_ld, mmdfn_gcnii_layer_bwd_ld, mmdfn_focal_loss_{fwd,bwd}_ignore and mmdfn_focal_loss_fwd_grad). */
@@ -327,6 +328,30 @@ int mmdfn_linear_planes_group(int n, const float* const* X, const void* const* p
                               const float* const* bias2, const int* n1, float* const* Y, const int* R, const int* K,
                               const int* N, const int* ldx, const int* ldy, int act, int accumulate,
                               const float* const* mask, float mask_scale, void* stream);
+/* ABI 20: the same with an optional dropout on the INPUT rows of a problem: xmask (may be null, entries may be null): R[i] x K[i]
+ * keep flags (0 / 1, contiguous, 16-byte aligned); problem i contracts (X_i * xmask_i) * xscale, formed where the launch stages
+ * its X rows (the forward of nn.GRU's inter-layer dropout, model.py:866, inside the second layer's input contraction), and
+ * writes those rows to xdrop[i] (R[i] x K[i] contiguous, may be null) for the layer's weight gradients.  A problem without
+ * xmask is mmdfn_linear_planes_group's, bit for bit. */
+int mmdfn_linear_planes_group_in(int n, const float* const* X, const void* const* planes, const float* const* bias,
+                                 const float* const* bias2, const int* n1, float* const* Y, const int* R, const int* K,
+                                 const int* N, const int* ldx, const int* ldy, int act, int accumulate,
+                                 const float* const* mask, float mask_scale, const float* const* xmask,
+                                 float* const* xdrop, float xscale, void* stream);
+/* ABI 20: the same with the PARTY-ORDERED STORE (replaces the mmdfn_party_gather launch behind the first party-GRU layer's input
+ * contraction, model.py:1070-1090): party (may be null: none) names, per problem, the speaker-encoded modality m whose utterance
+ * rows (t, b) = row t B + b the problem projects (R[i] == L B), or -1.  A party problem stores row (t, b) of X [W1; W2]^T +
+ * [b1; b2] to S[rank(t, b, p), (m B + b) P + p, :] for every speaker p flagged in qmask[t, b, :] (qmask: (L, B, P) floats;
+ * S: (L, Mn B P, N); Y[i] unused, may be null); extra workgroups of the launch write rank (L, B, P) int32 (-1: not flagged) and
+ * the bias into the padding rows k >= count(b, p) of S.  S and rank are bit for bit what mmdfn_party_gather makes of the
+ * bias-free projection.  The party problems come first, one per modality 0 .. Mn-1, with equal N / n1 (multiples of 4); act ==
+ * 0, accumulate == 0.  Returns -2 for a shape the store does not cover (L > 2048, P > 16, L B P > 24 576). */
+int mmdfn_linear_planes_group_party(int n, const float* const* X, const void* const* planes, const float* const* bias,
+                                    const float* const* bias2, const int* n1, float* const* Y, const int* R, const int* K,
+                                    const int* N, const int* ldx, const int* ldy, int act, int accumulate,
+                                    const float* const* mask, float mask_scale, const float* const* xmask,
+                                    float* const* xdrop, float xscale, const int* party, const float* qmask, float* S,
+                                    int32_t* rank, int L, int B, int P, int Mn, void* stream);
 
 /* A GROUP of few-row projections in one launch (linear_small.hip; n <= 8 problems, K <= 768, K % 4 == 0):
  *   Y_p = act(X_p W_p^T + b_p) (+ Y_p)      X_p: R_p rows of K_p floats (stride ldx), Y_p: R_p x N_p (stride ldy)
@@ -348,6 +373,18 @@ int mmdfn_linear_group_addend(int n, const float* const* X, const float* const* 
                               const float* const* bias, const float* const* bias2, float* const* Y, const float* const* Z,
                               const int* ldz, const int* R, const int* K, const int* N, const int* ldx, const int* ldw,
                               const int* ldy, const int* kmajor, const int* accumulate, int act, void* stream);
+/* ABI 20: the same with an optional SECOND K segment per problem: Y_p = X_p . W_p + X2_p . Wk2_p (+ Z_p) for X2[p] != NULL
+ * (kmajor[p] != 0 only; X2_p: R_p rows of K2[p] floats, row stride ldx2[p]; Wk2_p: (K2, N) with n-contiguous rows of stride
+ * ldw2[p]; 16-byte aligned, K2 % 4 == 0).  One workgroup contracts both operand pairs, each padded to whole 64-wide chunks: the
+ * input gradient that reaches the same rows through two projections (the party and the context GRU's first-layer input
+ * contractions of the text rows, model.py:1082,1132) is one launch and one accumulation chain.  X2 == NULL or X2[p] == NULL:
+ * the problem is mmdfn_linear_group_addend's, bit for bit.  Returns -2 when a second segment is asked for and the operands do
+ * not take the LDS-staged form (unaligned): the caller runs two launches. */
+int mmdfn_linear_group_seg2(int n, const float* const* X, const float* const* W, const float* const* W2, const int* N1,
+                            const float* const* bias, const float* const* bias2, float* const* Y, const float* const* Z,
+                            const int* ldz, const int* R, const int* K, const int* N, const int* ldx, const int* ldw,
+                            const int* ldy, const int* kmajor, const int* accumulate, const float* const* X2,
+                            const float* const* Wk2, const int* K2, const int* ldx2, const int* ldw2, int act, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Secondary fusion modules (fusion.hip); their dense projections go through mmdfn_linear_group.

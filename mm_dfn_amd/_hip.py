@@ -51,9 +51,13 @@ SIGNATURES = {
     "mmdfn_cut_weight_planes": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mmdfn_linear_planes": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "mmdfn_linear_planes_group": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P],
+    "mmdfn_linear_planes_group_in": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _F, _P],
+    "mmdfn_linear_planes_group_party": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _F,
+                                        _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "mmdfn_linear_group_supported": [_I, _I, _I],
     "mmdfn_linear_group": [_I] + [_P] * 15 + [_I, _P],
     "mmdfn_linear_group_addend": [_I] + [_P] * 17 + [_I, _P],
+    "mmdfn_linear_group_seg2": [_I] + [_P] * 22 + [_I, _P],
     "mmdfn_softmax_scale_fwd": [_P, _P, _P, _P, _I, _I, _P],
     "mmdfn_softmax_scale_bwd": [_P, _P, _P, _P, _P, _I, _I, _P],
     "mmdfn_mfn_mem_fwd": [_P] * 6 + [_L, _P],
@@ -108,7 +112,7 @@ SIGNATURES = {
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class HipLibraryError(RuntimeError):

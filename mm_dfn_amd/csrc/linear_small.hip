@@ -42,6 +42,10 @@ struct SmallGroup {
     int R[SG_MAX], K[SG_MAX], N[SG_MAX], N1[SG_MAX], ldx[SG_MAX], ldw[SG_MAX], ldy[SG_MAX], kmajor[SG_MAX], accumulate[SG_MAX];
     int tile0[SG_MAX + 1];
     int ntn[SG_MAX];
+    // second K segment (LDS-staged form, KMAJOR problems only; K2 == 0: none):  Y = X . W + X2 . Wk2 (+ Z)
+    const float* X2[SG_MAX];
+    const float* Wk2[SG_MAX];    // (K2, N), n-contiguous rows of stride ldw2
+    int K2[SG_MAX], ldx2[SG_MAX], ldw2[SG_MAX];
 };
 
 // ABL (tuning build, timing only): 1 no MFMA, 2 no operand loads, 4 no reduction / epilogue
@@ -326,22 +330,43 @@ __global__ __launch_bounds__(256) void linear_lds_kernel(SmallGroup G) {
             wsrc[i] = ((cc < N1) ? W + (int64_t)cc * ldw : W2 + (int64_t)(cc - N1) * ldw) + 4 * u;
         }
     }
-    // running sources: every issue moves them one chunk along k; only the LAST chunk can hold units past K, fetched from the zero block
-    const int64_t wstep = kmajor ? (int64_t)DK * ldw : DK;         // floats per chunk along the weight source
+    // running sources: every issue moves them one chunk along k; only the LAST chunk of a segment can hold units past its K,
+    // fetched from the zero block.  A second segment (K2 > 0) follows the first in whole chunks: when the first segment's chunks
+    // are issued the sources switch to (X2, Wk2).
+    int64_t wstep = kmajor ? (int64_t)DK * ldw : DK;               // floats per chunk along the weight source
     const void* const zero = &g_zero16;
-    const int nj = (K + DK - 1) / DK;
+    const int K2 = G.K2[p];
+    const int nj1 = (K + DK - 1) / DK;
+    const int nj = nj1 + (K2 + DK - 1) / DK;
     int issued = 0;
     uint32_t wr = lds0;                                            // LDS byte address of the stage the next issue fills
     auto issue = [&]() {
         if (ABL & 2) return;
         const void* sa[NA];
         const void* sb[4];
-        if (issued == nj - 1) {
-            const int k0 = DK * issued;
+        if (issued == nj1 && K2 > 0) {                             // (uniform) the second segment starts
+            const float* __restrict__ X2 = G.X2[p];
+            const float* __restrict__ Wk2 = G.Wk2[p];
+            const int ldx2 = G.ldx2[p], ldw2 = G.ldw2[p];
 #pragma unroll
-            for (int i = 0; i < NA; ++i) sa[i] = (k0 + xk[i] < K) ? (const void*)xsrc[i] : zero;
+            for (int i = 0; i < NA; ++i) {
+                const int r = row0 + 4 * (NA * w + i) + prow;
+                xsrc[i] = X2 + (int64_t)(r < R ? r : R - 1) * ldx2 + xk[i];
+            }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) sb[i] = (k0 + wk[i] < K) ? (const void*)wsrc[i] : zero;
+            for (int i = 0; i < 4; ++i) {
+                const int c = col0 + 4 * (pos ^ (((wk[i] >> 2) & 1) << 2));
+                wsrc[i] = Wk2 + (int64_t)wk[i] * ldw2 + (c + 3 < N ? c : 0);
+            }
+            wstep = (int64_t)DK * ldw2;
+        }
+        if (issued == nj1 - 1 || issued == nj - 1) {
+            const int k0 = issued < nj1 ? DK * issued : DK * (issued - nj1);
+            const int Ks = issued < nj1 ? K : K2;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) sa[i] = (k0 + xk[i] < Ks) ? (const void*)xsrc[i] : zero;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sb[i] = (k0 + wk[i] < Ks) ? (const void*)wsrc[i] : zero;
         } else {
 #pragma unroll
             for (int i = 0; i < NA; ++i) sa[i] = xsrc[i];
@@ -395,10 +420,11 @@ __global__ __launch_bounds__(256) void linear_lds_kernel(SmallGroup G) {
         }
         __syncthreads();
         if (issued < nj) issue();                                  // into the stage chunk j-1 was read from (all waves are past it)
-        const int kw = DK * j + 16 * NC * kp;                      // first k of this wave's part of the chunk
+        const int kw = DK * (j < nj1 ? j : j - nj1) + 16 * NC * kp;    // first k (of its segment) of this wave's part of the chunk
+        const int Ks = j < nj1 ? K : K2;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            if (kw + 16 * c >= K) continue;                        // (wave-uniform) nothing but staged zeros from here on
+            if (kw + 16 * c >= Ks) continue;                       // (wave-uniform) nothing but staged zeros from here on
             float4 av[2], bv[2];
 #pragma unroll
             for (int q = 0; q < 2; ++q) av[q] = *reinterpret_cast<const float4*>(s + aoff[q][c]);
@@ -518,6 +544,16 @@ extern "C" int mmdfn_linear_group_addend(int n, const float* const* X, const flo
                                          const float* const* Z, const int* ldz, const int* R, const int* K, const int* N,
                                          const int* ldx, const int* ldw, const int* ldy, const int* kmajor, const int* accumulate,
                                          int act, void* stream) {
+    return mmdfn_linear_group_seg2(n, X, W, W2, N1, bias, bias2, Y, Z, ldz, R, K, N, ldx, ldw, ldy, kmajor, accumulate, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, act, stream);
+}
+
+extern "C" int mmdfn_linear_group_seg2(int n, const float* const* X, const float* const* W, const float* const* W2,
+                                       const int* N1, const float* const* bias, const float* const* bias2, float* const* Y,
+                                       const float* const* Z, const int* ldz, const int* R, const int* K, const int* N,
+                                       const int* ldx, const int* ldw, const int* ldy, const int* kmajor, const int* accumulate,
+                                       const float* const* X2, const float* const* Wk2, const int* K2, const int* ldx2,
+                                       const int* ldw2, int act, void* stream) {
     if (n <= 0 || n > SG_MAX) return -1;
     SmallGroup G;
     G.n = n;
@@ -531,6 +567,10 @@ extern "C" int mmdfn_linear_group_addend(int n, const float* const* X, const flo
         if (!kmajor[p] && N1[p] < N[p] && (reinterpret_cast<uintptr_t>(W2[p]) & 15)) lds = false;
         t64 += (int64_t)((R[p] + 63) / 64) * ((N[p] + TN - 1) / TN);
     }
+    // a second K segment exists in the LDS-staged form only; the register form refuses it (the caller runs two launches)
+    bool seg2 = false;
+    for (int p = 0; p < n; ++p) seg2 = seg2 || (X2 != nullptr && X2[p] != nullptr);
+    if (seg2 && !lds) return -2;
     // 64-row tiles once they fill the chip on their own (2 workgroups per CU) AND the contraction is long (measured: 7 040 x 600
     // -> 200: 29.9 us against 33.3 us with 32-row tiles; at K = 200 the 32-row tiles win, 3 520 x 200 -> 600: 19.2 against 21.5 us);
     // 32-row tiles (k split across waves) otherwise
@@ -562,6 +602,14 @@ extern "C" int mmdfn_linear_group_addend(int n, const float* const* X, const flo
         G.accumulate[p] = (ext || accumulate[p]) ? 1 : 0;
         G.Z[p] = ext ? Z[p] : Y[p];
         G.ldz[p] = ext ? ldz[p] : ldy[p];
+        G.X2[p] = nullptr; G.Wk2[p] = nullptr; G.K2[p] = 0; G.ldx2[p] = 0; G.ldw2[p] = 0;
+        if (seg2 && X2[p] != nullptr) {
+            if (!kmajor[p] || !Wk2 || !Wk2[p] || !K2 || !ldx2 || !ldw2 || K2[p] < 4 || (K2[p] & 3) || (ldx2[p] & 3) || ldx2[p] < K2[p]
+                || (ldw2[p] & 3) || ldw2[p] < N[p] || (reinterpret_cast<uintptr_t>(X2[p]) & 15)
+                || (reinterpret_cast<uintptr_t>(Wk2[p]) & 15))
+                return -1;
+            G.X2[p] = X2[p]; G.Wk2[p] = Wk2[p]; G.K2[p] = K2[p]; G.ldx2[p] = ldx2[p]; G.ldw2[p] = ldw2[p];
+        }
         G.ntn[p] = (N[p] + tn - 1) / tn;
         G.tile0[p] = t0;
         t0 += ((R[p] + tm - 1) / tm) * G.ntn[p];

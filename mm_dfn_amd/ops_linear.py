@@ -31,8 +31,11 @@ def linear_group_raw(problems, act=0):
     """One launch for up to 8 few-row projections (csrc/linear_small.hip).  Each problem is a dict: x (R, K) fp32 rows,
     either ``w`` (N, K) [+ ``w2`` (N2, K): second row block] with optional ``b`` / ``b2``, or ``wk`` (K, N) (n-contiguous:
     y = x @ wk); optional ``out`` (+ ``accumulate``: y += ...), optional ``addend`` (R, N): y = ... + addend, out of place
-    (the addend is only read).  Returns the outputs."""
+    (the addend is only read).  A ``wk`` problem may name a second operand pair ``x2`` (R, K2) / ``wk2`` (K2, N):
+    y = x @ wk + x2 @ wk2 (+ addend), both contracted by the same workgroups (LDS-staged form only: returns None when the
+    operands do not take it, and the caller runs two launches).  Returns the outputs."""
     n = len(problems)
+    X2, WK2, K2, ldx2, ldw2 = [], [], [], [], []
     X, W, W2, B1, B2, Y, Z = [], [], [], [], [], [], []
     R, K, N, N1, ldx, ldw, ldy, ldz, km, acc = [], [], [], [], [], [], [], [], [], []
     for q in problems:
@@ -71,9 +74,31 @@ def linear_group_raw(problems, act=0):
                 z = z.contiguous()
             _hip.require_cuda(z)
         Z.append(z); ldz.append(z.stride(0) if z is not None else 0)
+        xb, wb = q.get("x2"), q.get("wk2")
+        if xb is not None:
+            if "wk" not in q or wb is None or xb.dtype != torch.float32 or xb.dim() != 2 or xb.shape[0] != x.shape[0] \
+                    or tuple(wb.shape) != (xb.shape[1], n_):
+                raise ValueError("linear_group_raw: a second segment needs wk, x2 (R, K2) and wk2 (K2, N)")
+            if xb.stride(1) != 1 or xb.stride(0) % 4 or xb.data_ptr() % 16:
+                xb = xb.contiguous()
+            if not (wb.stride(1) == 1 and wb.data_ptr() % 16 == 0 and wb.stride(0) % 4 == 0):
+                wb = wb.contiguous().clone()
+            _hip.require_cuda(xb, wb)
+            _hip.require_f32(xb, wb)
+        X2.append(xb); WK2.append(wb if xb is not None else None)
+        K2.append(xb.shape[1] if xb is not None else 0)
+        ldx2.append(xb.stride(0) if xb is not None else 0); ldw2.append(wb.stride(0) if xb is not None else 0)
     _hip.require_cuda(*X, *W)
     _hip.require_f32(*X, *W)
     ia, pa = _hip.int_array, _hip.ptr_array
+    if any(xb is not None for xb in X2):
+        rc = _hip.lib().mmdfn_linear_group_seg2(n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
+                                                ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), pa(X2), pa(WK2),
+                                                ia(K2), ia(ldx2), ia(ldw2), int(act), _hip.stream())
+        if rc == -2:
+            return None
+        _hip.check(rc, "mmdfn_linear_group_seg2")
+        return Y
     if any(z is not None for z in Z):
         rc = _hip.lib().mmdfn_linear_group_addend(n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
                                                   ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), int(act),
@@ -554,11 +579,17 @@ def linear_planes_raw(x2, w1, w2=None, b1=None, b2=None, transposed=False, act=0
     return out
 
 
-def linear_planes_group_raw(problems, transposed=False, act=0, mask_scale=1.0):
-    """Up to four independent products x2 B^T + [b1; b2] against piece planes in ONE launch (mmdfn_linear_planes_group).
+def linear_planes_group_raw(problems, transposed=False, act=0, mask_scale=1.0, xscale=1.0, party=None):
+    """Up to four independent products x2 B^T + [b1; b2] against piece planes in ONE launch (mmdfn_linear_planes_group_in).
     problems: dicts with x (2-D), w1, w2 and optionally b1, b2, out, mask (keep flags with the OUTPUT's element count: the
-    result is multiplied by mask * mask_scale); returns the outputs.  Every problem's result is
-    bit-identical to its own linear_planes_raw launch (it keeps the tile form it takes alone)."""
+    result is multiplied by mask * mask_scale), xmask (keep flags with the INPUT's element count: the product runs on
+    (x * xmask) * xscale, formed in the launch's staging step) and xdrop (with xmask: receives those dropped inputs); returns
+    the outputs.  Every problem's result is bit-identical to its own linear_planes_raw launch (it keeps the tile form it
+    takes alone) on the inputs it contracts.
+    ``party`` = dict(qmask (L, B, P), S (L, Mn B P, N), rank (L, B, P) int32): the problems that carry ``party_m`` (a modality index;
+    they come first, one per modality, at most four problems in all) store their rows in party order into S instead of an output
+    of their own (None in the returned list), and the launch also writes rank and the padding rows of S
+    (mmdfn_linear_planes_group_party); returns None when the shape is not covered (nothing was launched)."""
     lib = _hip.lib()
     xs, ents, outs = [], [], []
     for pr in problems:
@@ -571,26 +602,57 @@ def linear_planes_group_raw(problems, transposed=False, act=0, mask_scale=1.0):
         if x2.shape[1] != e.K:
             raise ValueError("linear_planes_group_raw: contraction width %d, planes were cut for %d" % (x2.shape[1], e.K))
         out = pr.get("out")
-        if out is None:
+        if out is None and pr.get("party_m") is None:
             out = torch.empty(x2.shape[0], e.N, dtype=torch.float32, device=x2.device)
         mk = pr.get("mask")
-        if mk is not None and (mk.numel() != out.numel() or mk.dtype != torch.float32 or not mk.is_contiguous() or out.stride(0) != e.N):
+        if mk is not None and (out is None or mk.numel() != out.numel() or mk.dtype != torch.float32 or not mk.is_contiguous() or out.stride(0) != e.N):
             raise _hip.HipLibraryError("linear_planes_group_raw: mask must be contiguous fp32 flags of the (contiguous) output's size")
+        xm, xd = pr.get("xmask"), pr.get("xdrop")
+        if xm is not None and (xm.numel() != x2.numel() or xm.dtype != torch.float32 or not xm.is_contiguous() or xm.data_ptr() % 16
+                               or (xd is not None and (xd.numel() != x2.numel() or xd.dtype != torch.float32
+                                                       or not xd.is_contiguous() or xd.data_ptr() % 16))):
+            raise _hip.HipLibraryError("linear_planes_group_raw: xmask / xdrop must be contiguous 16-byte aligned fp32 of the input's size")
         xs.append(x2)
         ents.append(e)
         outs.append(out)
+    if party is not None:
+        if len(problems) > 4 or transposed:
+            raise ValueError("linear_planes_group_raw: the party-ordered store takes one forward launch of at most four problems")
+        qm, S, rank = party["qmask"], party["S"], party["rank"]
+        L, B, P = qm.shape
+        _hip.require_cuda(qm, S, rank)
+        if not (qm.is_contiguous() and qm.dtype == torch.float32 and S.is_contiguous() and rank.is_contiguous()
+                and rank.dtype == torch.int32):
+            raise _hip.HipLibraryError("linear_planes_group_raw: qmask / S / rank must be contiguous fp32 / fp32 / int32")
+        pm = [pr.get("party_m", -1) if pr.get("party_m") is not None else -1 for pr in problems]
+        Mn = sum(1 for v in pm if v >= 0)
+        n1 = [e.N if pr.get("w2") is None else e.n1 for pr, e in zip(problems, ents)]
+        rc = lib.mmdfn_linear_planes_group_party(
+            len(problems), _hip.ptr_array(xs), _hip.ptr_array([e.buf for e in ents]),
+            _hip.ptr_array([pr.get("b1") for pr in problems]), _hip.ptr_array([pr.get("b2") for pr in problems]),
+            _hip.int_array(n1), _hip.ptr_array(outs), _hip.int_array([x.shape[0] for x in xs]),
+            _hip.int_array([e.K for e in ents]), _hip.int_array([e.N for e in ents]), _hip.int_array([x.stride(0) for x in xs]),
+            _hip.int_array([0 if o is None else o.stride(0) for o in outs]), int(act), 0,
+            _hip.ptr_array([pr.get("mask") for pr in problems]), float(mask_scale),
+            _hip.ptr_array([pr.get("xmask") for pr in problems]), _hip.ptr_array([pr.get("xdrop") for pr in problems]),
+            float(xscale), _hip.int_array(pm), _hip.ptr(qm), _hip.ptr(S), _hip.ptr(rank), L, B, P, Mn, _hip.stream())
+        if rc == -2:
+            return None
+        _hip.check(rc, "mmdfn_linear_planes_group_party")
+        return outs
     for i in range(0, len(problems), 4):
         sl = slice(i, i + 4)
         prs, x4, e4, o4 = problems[sl], xs[sl], ents[sl], outs[sl]
         n1 = [e.N if (transposed or pr.get("w2") is None) else e.n1 for pr, e in zip(prs, e4)]
-        rc = lib.mmdfn_linear_planes_group(len(prs), _hip.ptr_array(x4), _hip.ptr_array([e.buf for e in e4]),
+        rc = lib.mmdfn_linear_planes_group_in(len(prs), _hip.ptr_array(x4), _hip.ptr_array([e.buf for e in e4]),
                                            _hip.ptr_array([pr.get("b1") for pr in prs]), _hip.ptr_array([pr.get("b2") for pr in prs]),
                                            _hip.int_array(n1), _hip.ptr_array(o4), _hip.int_array([x.shape[0] for x in x4]),
                                            _hip.int_array([e.K for e in e4]), _hip.int_array([e.N for e in e4]),
                                            _hip.int_array([x.stride(0) for x in x4]), _hip.int_array([o.stride(0) for o in o4]),
                                            int(act), 0, _hip.ptr_array([pr.get("mask") for pr in prs]), float(mask_scale),
-                                           _hip.stream())
-        _hip.check(rc, "mmdfn_linear_planes_group")
+                                           _hip.ptr_array([pr.get("xmask") for pr in prs]),
+                                           _hip.ptr_array([pr.get("xdrop") for pr in prs]), float(xscale), _hip.stream())
+        _hip.check(rc, "mmdfn_linear_planes_group_in")
     return outs
 
 
@@ -599,25 +661,38 @@ class _Linear2Group(torch.autograd.Function):
     hoisted input contractions of one layer) as ONE node: one grouped launch against the weights' piece planes forward, one for
     the input gradients; weight / bias gradients per group as in _Linear2.  args: (x, w1, w2, b1, b2) per group.
     ``masks`` (optional, keep flags per group) / ``scale``: the inputs pass through a dropout first (nn.GRU's between its layers):
-    x_g * mask_g * scale is formed by ONE launch for all groups here, and the dropout's backward is the input-gradient launch's
-    epilogue instead of a launch of its own."""
+    (x_g * mask_g) * scale is formed in the projection launch's staging step, which also writes the dropped rows out for the
+    weight gradients (FUSE_INPUT_DROPOUT; otherwise by ONE mask_scale launch for all groups in front), and the dropout's backward
+    is the input-gradient launch's epilogue instead of a launch of its own."""
 
     @staticmethod
     def forward(ctx, n, masks, scale, *args):
         grp = [args[5 * g:5 * g + 5] for g in range(n)]
         shapes, x2s = [], []
+        fused = False
         if masks is not None:
-            from .ops_flags import _MaskScale
             xin = [x.contiguous() for x, *_ in grp]
             dropped = [torch.empty_like(x) for x in xin]
-            _MaskScale._launch(xin, list(masks), dropped, float(scale))
-        for g, (x, w1, w2, b1, b2) in enumerate(grp):
-            shapes.append(x.shape)
-            x2 = (dropped[g] if masks is not None else x).reshape(-1, x.shape[-1])
-            if x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
-                x2 = x2.contiguous()
-            x2s.append(x2)
-        ys = linear_planes_group_raw([dict(x=x2, w1=w1, w2=w2, b1=b1, b2=b2) for x2, (_, w1, w2, b1, b2) in zip(x2s, grp)])
+            fused = FUSE_INPUT_DROPOUT and all(m.dtype == torch.float32 and m.is_contiguous() and m.data_ptr() % 16 == 0
+                                               and x.data_ptr() % 16 == 0 for m, x in zip(masks, xin))
+            if not fused:
+                from .ops_flags import _MaskScale
+                _MaskScale._launch(xin, list(masks), dropped, float(scale))
+        if fused:
+            probs = []
+            for g, (x, w1, w2, b1, b2) in enumerate(grp):
+                shapes.append(x.shape)
+                x2s.append(dropped[g].view(-1, x.shape[-1]))
+                probs.append(dict(x=xin[g].view(-1, x.shape[-1]), w1=w1, w2=w2, b1=b1, b2=b2, xmask=masks[g], xdrop=x2s[g]))
+            ys = linear_planes_group_raw(probs, xscale=float(scale))
+        else:
+            for g, (x, w1, w2, b1, b2) in enumerate(grp):
+                shapes.append(x.shape)
+                x2 = (dropped[g] if masks is not None else x).reshape(-1, x.shape[-1])
+                if x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
+                    x2 = x2.contiguous()
+                x2s.append(x2)
+            ys = linear_planes_group_raw([dict(x=x2, w1=w1, w2=w2, b1=b1, b2=b2) for x2, (_, w1, w2, b1, b2) in zip(x2s, grp)])
         ctx.n = n
         ctx.masks = None if masks is None else list(masks)
         ctx.scale = float(scale)
@@ -673,6 +748,8 @@ def linear2_group(groups, masks=None, scale=1.0):
 
 
 LINEAR2_FEW_ROWS = 2048
+# _Linear2Group: the dropout on the inputs runs in the projection launch's staging step ("0": a mask_scale launch in front; A/B aid)
+FUSE_INPUT_DROPOUT = __import__("os").environ.get("MMDFN_FUSE_INPUT_DROPOUT", "1") != "0"
 GROUP_ROWS = 4096          # _LinearGroup: row count up to which a group of projections runs as one few-row launch
 
 

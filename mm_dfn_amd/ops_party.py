@@ -107,10 +107,19 @@ def _queue_bias_halves(A, b1, b2, n1, slabs=None):
         torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
 
 
+# _ProjectGather.forward: the plane projection stores its rows in party order and writes rank and the padding rows itself ("0": the
+# projection in utterance order, then the gather launch; A/B aid)
+PARTY_ORDERED_STORE = __import__("os").environ.get("MMDFN_PARTY_ORDERED_STORE", "1") != "0"
+# _ProjectGather.backward: a rider's input gradient as second K segment of its source modality's problem ("0": the accumulating
+# launch behind it; A/B aid)
+RIDER_DX_SEGMENT = __import__("os").environ.get("MMDFN_RIDER_DX_SEGMENT", "1") != "0"
+
+
 class _ProjectGather(torch.autograd.Function):
     """First party-GRU layer without projecting padded party rows: gi_p = party_gather(X_m [W1; W2]^T) + [b1; b2] for every
-    speaker-encoded modality m, as ONE node: a grouped launch of the few-row kernel for the projections (each modality its
-    own problem, no stacked copy), the gather kernel, and on the way back the scatter, ONE grouped K-major launch for the
+    speaker-encoded modality m, as ONE node: a grouped launch for the projections (each modality its own problem, no stacked
+    copy) that stores its rows in party order and writes rank and the padding rows itself where the plane form applies
+    (PARTY_ORDERED_STORE), else a grouped projection launch and the gather kernel; on the way back the scatter, ONE grouped K-major launch for the
     input gradients (accumulated onto the gradient that reaches X_m through its passthrough alias), the column-sum kernel
     for the bias gradient and queued weight-gradient segments.  Outputs: (gi_p (L, Mn*B*P, N), rank, X_0', .., X_{Mn-1}')
     with X_m' identities of the inputs (see _PartyGather)."""
@@ -132,30 +141,42 @@ class _ProjectGather(torch.autograd.Function):
         Mn = len(mods)
         w1c, w2c = w1.contiguous(), w2.contiguous()
         n1, N = w1.shape[0], w1.shape[0] + w2.shape[0]
-        G = torch.empty(Mn, L * B, N, dtype=torch.float32, device=qmask.device)
         routs = [torch.empty(L * B, pr[0].shape[0] + pr[1].shape[0], dtype=torch.float32, device=qmask.device) for pr in rprm]
         nprob = Mn + nr
-        if (nprob <= 4 and nprob * L * B >= ops_linear.PLANES_MIN_ROWS and ops_linear.planes_supported(w1, w2)
-                and all(ops_linear.planes_supported(pr[0], pr[1]) for pr in rprm)):
-            # enough rows for the plane form: the projections against the weights' piece planes (cut once per optimizer step),
-            # one grouped launch (4 x 1 760 rows at cfg2: 21 us against 25 for the few-row kernel)
-            probs = [dict(x=m.view(L * B, H), w1=w1, w2=w2, out=G[i]) for i, m in enumerate(mods)]
-            for (src, _), (rw1, rw2, rb1, rb2, _rw), o in zip(riders, rprm, routs):
-                probs.append(dict(x=mods[src].view(L * B, H), w1=rw1, w2=rw2, b1=rb1, b2=rb2, out=o))
-            ops_linear.linear_planes_group_raw(probs)
-        else:
-            probs = [dict(x=m.view(L * B, H), w=w1c, w2=w2c, out=G[i]) for i, m in enumerate(mods)]
-            for (src, _), (rw1, rw2, rb1, rb2, _rw), o in zip(riders, rprm, routs):
-                probs.append(dict(x=mods[src].view(L * B, H), w=rw1.contiguous(), w2=rw2.contiguous(), b=rb1, b2=rb2, out=o))
-            linear_group_raw(probs)
-        bias = None
-        if b1 is not None:
-            bias = bcat if bcat is not None else torch.cat([b1, b2])
         S = torch.empty(L, Mn * B * P, N, dtype=torch.float32, device=qmask.device)
         rank = torch.empty(L, B, P, dtype=torch.int32, device=qmask.device)
-        rc = _hip.lib().mmdfn_party_gather(Mn, _hip.ptr_array([G[i] for i in range(Mn)]), _hip.ptr(qmask), _hip.ptr(bias),
-                                           _hip.ptr(S), _hip.ptr(rank), L, B, P, N, _hip.stream())
-        _hip.check(rc, "mmdfn_party_gather")
+        planes = (nprob <= 4 and nprob * L * B >= ops_linear.PLANES_MIN_ROWS and ops_linear.planes_supported(w1, w2)
+                  and all(ops_linear.planes_supported(pr[0], pr[1]) for pr in rprm))
+        stored = False
+        if (planes and PARTY_ORDERED_STORE and qmask.dtype == torch.float32 and n1 % 4 == 0 and (b1 is None) == (b2 is None)
+                and L <= 2048 and P <= 16 and L * B * P <= 24576):
+            # one launch: the party problems store every row where the party layout wants it (+ bias), extra workgroups write
+            # rank and the padding rows; the gate pre-activations are never materialised in utterance order
+            probs = [dict(x=m.view(L * B, H), w1=w1, w2=w2, b1=b1, b2=b2, party_m=i) for i, m in enumerate(mods)]
+            for (src, _), (rw1, rw2, rb1, rb2, _rw), o in zip(riders, rprm, routs):
+                probs.append(dict(x=mods[src].view(L * B, H), w1=rw1, w2=rw2, b1=rb1, b2=rb2, out=o))
+            stored = ops_linear.linear_planes_group_raw(probs, party=dict(qmask=qmask, S=S, rank=rank)) is not None
+        if not stored:
+            # two launches: the projections in utterance order (bias-free), then the gather kernel (+ bias, rank)
+            G = torch.empty(Mn, L * B, N, dtype=torch.float32, device=qmask.device)
+            if planes:
+                # enough rows for the plane form: the projections against the weights' piece planes (cut once per optimizer
+                # step), one grouped launch (4 x 1 760 rows at cfg2: 21 us against 25 for the few-row kernel)
+                probs = [dict(x=m.view(L * B, H), w1=w1, w2=w2, out=G[i]) for i, m in enumerate(mods)]
+                for (src, _), (rw1, rw2, rb1, rb2, _rw), o in zip(riders, rprm, routs):
+                    probs.append(dict(x=mods[src].view(L * B, H), w1=rw1, w2=rw2, b1=rb1, b2=rb2, out=o))
+                ops_linear.linear_planes_group_raw(probs)
+            else:
+                probs = [dict(x=m.view(L * B, H), w=w1c, w2=w2c, out=G[i]) for i, m in enumerate(mods)]
+                for (src, _), (rw1, rw2, rb1, rb2, _rw), o in zip(riders, rprm, routs):
+                    probs.append(dict(x=mods[src].view(L * B, H), w=rw1.contiguous(), w2=rw2.contiguous(), b=rb1, b2=rb2, out=o))
+                linear_group_raw(probs)
+            bias = None
+            if b1 is not None:
+                bias = bcat if bcat is not None else torch.cat([b1, b2])
+            rc = _hip.lib().mmdfn_party_gather(Mn, _hip.ptr_array([G[i] for i in range(Mn)]), _hip.ptr(qmask), _hip.ptr(bias),
+                                               _hip.ptr(S), _hip.ptr(rank), L, B, P, N, _hip.stream())
+            _hip.check(rc, "mmdfn_party_gather")
         ctx.dims = (L, B, P, H, Mn, n1, N)
         ctx.refs = (w1, w2, b1, b2)
         ctx.riders = [(src, tuple(pr[:4])) for (src, _), pr in zip(riders, rprm)]
@@ -201,6 +222,7 @@ class _ProjectGather(torch.autograd.Function):
         # input gradients: dX_m = dG_m [W1; W2] (+ the gradient that reached X_m's alias), one grouped launch
         dXs = [None] * Mn
         need = [m for m in range(Mn) if ctx.needs_input_grad[8 + 5 * nr + m]]
+        absorbed, rdy2 = set(), {}              # riders whose input gradient the grouped launch contracted; their dY rows
         if need:
             # dX_m = dG_m [W1; W2] + (the gradient that reached X_m's passthrough alias), out of place: the incoming gradient is
             # only READ (the kernel's addend), never written -- autograd may hand the same tensor to several nodes (ADVICE r03;
@@ -210,13 +232,38 @@ class _ProjectGather(torch.autograd.Function):
                 d = dpass[m] if m < len(dpass) else None
                 adds.append(None if d is None else d.reshape(L * B, H))
             if wcat is not None:
-                probs = []
-                for m, d in zip(need, adds):
-                    q = dict(x=dG[m], wk=wcat)
-                    if d is not None:
-                        q.update(addend=d)
-                    probs.append(q)
-                res = linear_group_raw(probs)
+                # a rider's input gradient dgi . W_ih (stacked view) lands on its source modality's rows: the second K segment of
+                # that modality's problem -- one workgroup contracts both operand pairs (RIDER_DX_SEGMENT; one rider per source,
+                # operands the LDS-staged form takes; otherwise an accumulating launch behind this one, below)
+                seg = {}
+                if RIDER_DX_SEGMENT:
+                    for i, (src, _prm) in enumerate(ctx.riders):
+                        dyr = dride[i] if i < len(dride) else None
+                        if dyr is None or rwcat[i] is None or src not in need:
+                            continue
+                        if src in seg:
+                            seg[src] = None            # several riders on one source: today's launches
+                        else:
+                            seg[src] = i
+                    seg = {src: i for src, i in seg.items() if i is not None}
+                for src, i in seg.items():
+                    rdy2[i] = dride[i].reshape(L * B, -1).contiguous()
+
+                def problems(with_seg):
+                    probs = []
+                    for m, d in zip(need, adds):
+                        q = dict(x=dG[m], wk=wcat)
+                        if d is not None:
+                            q.update(addend=d)
+                        if with_seg and m in seg:
+                            q.update(x2=rdy2[seg[m]], wk2=rwcat[seg[m]])
+                        probs.append(q)
+                    return probs
+                res = linear_group_raw(problems(True)) if seg else None
+                if res is not None:
+                    absorbed = set(seg.values())
+                else:
+                    res = linear_group_raw(problems(False))
             else:
                 res = []
                 for m, d in zip(need, adds):
@@ -230,17 +277,18 @@ class _ProjectGather(torch.autograd.Function):
                 dXs[m] = o.view(L, B, H)
         else:
             dXs = [d for d in dpass] + [None] * (Mn - len(dpass))
-        # riders: their input gradient is added onto the source modality's (second launch: two workgroups of one launch may not
-        # write the same rows), their weight / bias gradients are queued like any projection's
+        # riders: their input gradient is added onto the source modality's (the second K segment of the launch above, or a
+        # second launch: two workgroups of one launch may not write the same rows), their weight / bias gradients are queued
+        # like any projection's
         rgrads = []
         for i, (src, (rp1, rp2, rb1, rb2)) in enumerate(ctx.riders):
             dyr = dride[i] if i < len(dride) else None
             if dyr is None:
                 rgrads += [None, None, None, None, None]
                 continue
-            dy2 = dyr.reshape(L * B, -1).contiguous()
+            dy2 = rdy2[i] if i in rdy2 else dyr.reshape(L * B, -1).contiguous()
             rn1 = rp1.shape[0]
-            if ctx.needs_input_grad[8 + 5 * nr + src]:
+            if ctx.needs_input_grad[8 + 5 * nr + src] and i not in absorbed:
                 if dXs[src] is None:
                     dXs[src] = torch.zeros(L, B, H, dtype=torch.float32, device=dev)
                 tgt = dXs[src].view(L * B, H)
