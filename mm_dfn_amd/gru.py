@@ -426,5 +426,5 @@ def bigru2(xs, grus, dropout=0.0, training=False, gi0=None, party=None):
         if layer == 0 and training and dropout > 0:
             # nn.GRU's dropout between the layers: 0 / 1 keep flags from the step's flag pool (no generator launch of its
             # own) applied to every group's output by ONE launch each way -- at the head of the next layer (see there)
-            pending = ([ops.keep_flags(y.numel(), dropout, y.device) for y in cur], ops.keep_scale(dropout))
+            pending = ([ops.keep_flags(y.numel(), dropout, y.device, site="gru") for y in cur], ops.keep_scale(dropout))
     return cur

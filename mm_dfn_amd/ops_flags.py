@@ -16,6 +16,11 @@ from . import _hip
 # A fresh tensor per draw: slices saved for backward are never overwritten.  Outside a scope every request draws its own.
 _FLAG_SCOPE = None
 _FLAG_HINT = {}
+# test tap (the idiom of gcn_stack.TAP): a list to which every ``keep_flags`` call appends (n, p, the tensor it returned, the
+# caller's site label) -- tests/util.dropout_tape_from_tap hands those flags to the oracle's dropout sites, so that a
+# dropout-on step (eager, or replayed from a captured graph: the tensors are the ones the graph rewrites) can be compared
+# with the oracle.  None (the default): nothing is kept.
+TAP = None
 
 
 class flag_pool:
@@ -170,9 +175,15 @@ def draw_flags(n, p, device, riders=None):
     return out
 
 
-def keep_flags(n, p, device):
-    """n fp32 keep flags (1 with probability 1 - p), 16-byte aligned."""
-    n = int(n)
+def keep_flags(n, p, device, site=None):
+    """n fp32 keep flags (1 with probability 1 - p), 16-byte aligned.  ``site``: the caller's label for the test tap."""
+    out = _keep_flags(int(n), p, device)
+    if TAP is not None:
+        TAP.append((int(n), float(p), out, site))
+    return out
+
+
+def _keep_flags(n, p, device):
     scope = _FLAG_SCOPE
     if scope is None:
         return draw_flags((n + 3) & ~3, p, device)[:n]

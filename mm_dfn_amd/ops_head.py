@@ -105,6 +105,6 @@ def head(Fm, weight, bias, p=0.0, training=False, relu=True):
     mask, mscale = None, 1.0
     if training and p > 0:
         N = Fm.shape[1] if Fm.dim() == 3 else Fm.shape[0]
-        mask = keep_flags(N * _head_width(Fm), p, Fm.device).view(N, _head_width(Fm))
+        mask = keep_flags(N * _head_width(Fm), p, Fm.device, site="head").view(N, _head_width(Fm))
         mscale = keep_scale(p)
     return _Head.apply(Fm, mask, mscale, weight, bias, relu)

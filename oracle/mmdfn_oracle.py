@@ -69,6 +69,47 @@ def relu_site(pre, site):
 
 
 # ----------------------------------------------------------------------------
+# Dropout tape (a test aid of the oracle itself, like the ReLU probe).  Every dropout of the restated path goes through
+# ``dropout_site``.  With no tape set it is F.dropout, as before.  With a tape set an active site (training, p > 0) asks the
+# tape for its 0 / 1 keep mask and returns x * mask / (1 - p): a test hands the oracle the flags the device drew and both
+# sides compute the same function.  A site whose mask is None is the identity.  ``seen`` lists (site, shape) in call order.
+# Site names: "lstm_l" (context GRU, between its layers), "party.<a|v|l>.<speaker>" (one per pass of party_encode),
+# "<stack prefix>x" / "h0" / "conv<i>" (GCNII_lyc), "<stack prefix>out" (GCNII's single dropout behind the loop), "head".
+# ----------------------------------------------------------------------------
+class DropoutTape:
+    def __init__(self, masks=None):
+        self.masks = dict(masks or {})     # site -> 0 / 1 tensor of the site's shape (any dtype), or None / absent: identity
+        self.seen = []                     # (site, shape) of every active site, in call order
+
+    def mask(self, site, x):
+        self.seen.append((site, tuple(x.shape)))
+        return self.masks.get(site)
+
+
+_DROPOUT_TAPE = None
+
+
+def set_dropout_tape(tape):
+    global _DROPOUT_TAPE
+    prev, _DROPOUT_TAPE = _DROPOUT_TAPE, tape
+    return prev
+
+
+def dropout_site(x, p, training, site):
+    tape = _DROPOUT_TAPE
+    if tape is None:
+        return F.dropout(x, p, training)
+    if not training or p <= 0:
+        return x
+    m = tape.mask(site, x)
+    if m is None:
+        return x
+    if tuple(m.shape) != tuple(x.shape):
+        raise ValueError("dropout site %s: mask %s for a tensor %s" % (site, tuple(m.shape), tuple(x.shape)))
+    return x * m.to(x.dtype) * (1.0 / (1.0 - p))
+
+
+# ----------------------------------------------------------------------------
 # recurrent cells (the equations torch.nn.GRU / torch.nn.LSTM document; the
 # reference calls those modules at model.py:866,868 and model_GCN.py:433)
 # ----------------------------------------------------------------------------
@@ -96,13 +137,26 @@ def gru_direction(x, w_ih, w_hh, b_ih, b_hh, reverse):
     return torch.stack(outs, 0)
 
 
-def bigru2(x, params, prefix, dropout=0.0, training=False, engine="manual"):
+def bigru2(x, params, prefix, dropout=0.0, training=False, engine="manual", site=None):
     """2-layer bidirectional GRU, no packing (model.py:866,868,1082,1132).
 
     engine="manual": explicit equations above (the kernel's specification).
     engine="aten":   torch.nn.GRU with the same weights (what the reference
                      itself executes on CPU); used for the timed CPU baseline.
+    ``site``: the name of the dropout between the layers (DropoutTape).  nn.GRU(dropout=p) draws its own mask, so under a
+    tape the aten engine runs the two layers as two single-layer nn.GRU passes with ``dropout_site`` between them.
     """
+    site = prefix.rstrip(".") if site is None else site
+    if engine == "aten" and _DROPOUT_TAPE is not None and training and dropout > 0:
+        H = params[prefix + "weight_hh_l0"].shape[1]
+        cur = x
+        for layer in range(2):
+            g = torch.nn.GRU(cur.shape[-1], H, num_layers=1, bidirectional=True).to(x.dtype)
+            names = [n for n, _ in g.named_parameters()]
+            cur = torch.func.functional_call(g, {n: params[prefix + n.replace("_l0", "_l%d" % layer)] for n in names}, (cur,))[0]
+            if layer == 0:
+                cur = dropout_site(cur, dropout, True, site)
+        return cur
     if engine == "aten":
         H = params[prefix + "weight_hh_l0"].shape[1]
         g = torch.nn.GRU(x.shape[-1], H, num_layers=2, bidirectional=True, dropout=dropout)
@@ -118,7 +172,7 @@ def bigru2(x, params, prefix, dropout=0.0, training=False, engine="manual"):
                                       params[prefix + "bias_ih_" + tag], params[prefix + "bias_hh_" + tag], rev))
         cur = torch.cat(outs, -1)
         if layer == 0 and dropout > 0 and training:
-            cur = F.dropout(cur, dropout, True)
+            cur = dropout_site(cur, dropout, True, site)
     return cur
 
 
@@ -138,13 +192,14 @@ def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
 # ----------------------------------------------------------------------------
 # speaker-party encoder (model.py:1070-1090 / 1101-1121 / 1134-1154)
 # ----------------------------------------------------------------------------
-def party_encode(X, qmask, params, dropout=0.0, training=False, engine="manual"):
+def party_encode(X, qmask, params, dropout=0.0, training=False, engine="manual", site="party"):
     """For every speaker p: compact that speaker's utterances to the front of
     a zero (L, B, H) buffer, run the shared ``rnn_parties`` BiGRU over the
     full padded length, scatter the first k outputs back to the speaker's
     positions.  X: (L, B, H), qmask: (L, B, P).  Returns U_p: (L, B, H).
     The scatter ASSIGNS speaker by speaker (model.py:1084-1087): at an
-    utterance flagged for several speakers the last one's encoding wins."""
+    utterance flagged for several speakers the last one's encoding wins.
+    Dropout sites: ``site``.<p>, one per speaker pass, each (L, B, 2 * hidden) with time = the compacted position."""
     L, B, Hd = X.shape
     P = qmask.shape[2]
     Xb = X.transpose(0, 1)            # (B, L, H)
@@ -154,7 +209,8 @@ def party_encode(X, qmask, params, dropout=0.0, training=False, engine="manual")
     for p in range(P):
         rows = [F.pad(Xb[b][idx[b][p]], (0, 0, 0, L - idx[b][p].numel())) for b in range(B)]
         party = torch.stack(rows, 0)                               # (B, L, H), zeros past k
-        enc.append(bigru2(party.transpose(0, 1), params, "rnn_parties.", dropout, training, engine).transpose(0, 1))
+        enc.append(bigru2(party.transpose(0, 1), params, "rnn_parties.", dropout, training, engine,
+                          site="%s.%d" % (site, p)).transpose(0, 1))
     out = []
     for b in range(B):
         acc = torch.zeros(L, enc[0].shape[-1], dtype=X.dtype)
@@ -178,12 +234,12 @@ def encoders(params, U, qmask, lengths, U_a, U_v, cfg, training=False, engine="m
     w = cfg["speaker_weights"]
     p = cfg.get("dropout", 0.0)
     Xa = F.linear(U_a, params["linear_a.weight"], params["linear_a.bias"])
-    ea = Xa + w[0] * party_encode(Xa, qmask, params, p, training, engine)
+    ea = Xa + w[0] * party_encode(Xa, qmask, params, p, training, engine, "party.a")
     Xv = F.linear(U_v, params["linear_v.weight"], params["linear_v.bias"])
-    ev = Xv + w[1] * party_encode(Xv, qmask, params, p, training, engine)
+    ev = Xv + w[1] * party_encode(Xv, qmask, params, p, training, engine, "party.v")
     Xl = F.linear(U, params["linear_l.weight"], params["linear_l.bias"])
-    ctx = bigru2(Xl, params, "lstm_l.", p, training, engine)
-    el = ctx + w[2] * party_encode(Xl, qmask, params, p, training, engine)
+    ctx = bigru2(Xl, params, "lstm_l.", p, training, engine, site="lstm_l")
+    el = ctx + w[2] * party_encode(Xl, qmask, params, p, training, engine, "party.l")
     return [flatten_dialogues(e, lengths) for e in (ea, ev, el)]
 
 
@@ -311,9 +367,9 @@ def graph_convolution(x, adj, h0, lamda, alpha, l, weight):
 def gcnii_stack(x, adj, params, prefix, nlayers, lamda, alpha, dropout=0.0, training=False,
                 reason_flag=True, use_residue=True):
     """GCNII_lyc.forward with an explicit adjacency (return_feature=True)."""
-    x = F.dropout(x, dropout, training)
+    x = dropout_site(x, dropout, training, prefix + "x")
     h0 = relu_site(F.linear(x, params[prefix + "fcs.0.weight"], params[prefix + "fcs.0.bias"]), prefix + "fcs0")
-    cur = F.dropout(h0, dropout, training)
+    cur = dropout_site(h0, dropout, training, prefix + "h0")
     h = torch.zeros_like(cur)
     c = torch.zeros_like(cur)
     for i in range(nlayers):
@@ -324,7 +380,7 @@ def gcnii_stack(x, adj, params, prefix, nlayers, lamda, alpha, dropout=0.0, trai
             cur = h
         cur = relu_site(graph_convolution(cur, adj, h0, lamda, alpha, i + 1,
                                           params[prefix + "convs.%d.weight" % i]), prefix + "conv%d" % i)
-        cur = F.dropout(cur, dropout, training)
+        cur = dropout_site(cur, dropout, training, prefix + "conv%d" % i)
         if reason_flag:
             cur = cur + q
     return torch.cat([x, cur], -1) if use_residue else cur
@@ -335,9 +391,9 @@ def gcnii_deep(x, dia_len, params, prefix, nlayers, lamda=0.5, alpha=0.1, dropou
     """GCNII.forward (model_GCN.py:258-286): unimodal adjacency from x itself (create_big_adj :288-310 = the M = 1
     case), no dropout inside the layer loop (commented out at :275), one dropout after it (:279)."""
     adj = create_big_adj([x], dia_len)
-    x = F.dropout(x, dropout, training)
+    x = dropout_site(x, dropout, training, prefix + "x")
     h0 = torch.relu(F.linear(x, params[prefix + "fcs.0.weight"], params[prefix + "fcs.0.bias"]))
-    cur = F.dropout(h0, dropout, training)
+    cur = dropout_site(h0, dropout, training, prefix + "h0")
     h = torch.zeros_like(cur)
     c = torch.zeros_like(cur)
     for i in range(nlayers):
@@ -349,7 +405,7 @@ def gcnii_deep(x, dia_len, params, prefix, nlayers, lamda=0.5, alpha=0.1, dropou
         cur = torch.relu(graph_convolution(cur, adj, h0, lamda, alpha, i + 1, params[prefix + "convs.%d.weight" % i]))
         if reason_flag:
             cur = cur + q
-    cur = F.dropout(cur, dropout, training)
+    cur = dropout_site(cur, dropout, training, prefix + "out")
     return torch.cat([x, cur], -1) if use_residue else cur
 
 
@@ -375,6 +431,17 @@ def forward_deepgcn(params, U, qmask, umask, lengths, U_a, U_v, cfg, training=Fa
     return head(fused, params, cfg.get("dropout", 0.0), training)
 
 
+def forward_graph_free(params, U, qmask, umask, lengths, U_a, U_v, cfg, training=False, engine="manual"):
+    """DialogueGNNModel.forward for graph_type='None' with att_type 'concat_subsequently' / 'concat_only', three modalities
+    (model.py:1374-1404): E_m = [graph_net_m(f_m) | f_m] per modality, concatenated a, v, l, then dropout -> smax_fc ->
+    log_softmax WITHOUT a ReLU.  Dropout site: "head"."""
+    feats = encoders(params, U, qmask, lengths, U_a, U_v, cfg, training, engine)
+    e = [torch.cat([F.linear(f, params["graph_net_%s.weight" % k], params["graph_net_%s.bias" % k]), f], -1)
+         for f, k in zip(feats, "avl")]
+    z = dropout_site(torch.cat(e, -1), cfg.get("dropout", 0.0), training, "head")
+    return F.log_softmax(F.linear(z, params["smax_fc.weight"], params["smax_fc.bias"]), 1)
+
+
 def mm_gcn(feats, dia_len, params, cfg, training=False):
     """MM_GCN.forward, use_speaker/use_modal off (model_mm.py:77-120)."""
     adj = create_big_adj(feats, dia_len, cfg.get("modal_weight", 1.0))
@@ -389,7 +456,7 @@ def mm_gcn(feats, dia_len, params, cfg, training=False):
 # head + loss (model.py:1328-1337, loss.py:14-34)
 # ----------------------------------------------------------------------------
 def head(feat, params, dropout=0.0, training=False):
-    z = relu_site(F.dropout(feat, dropout, training), "head")
+    z = relu_site(dropout_site(feat, dropout, training, "head"), "head")
     return F.log_softmax(F.linear(z, params["smax_fc.weight"], params["smax_fc.bias"]), 1)
 
 

@@ -407,8 +407,83 @@ def export_dataloader():
     print("dataloader ok")
 
 
+DROPOUT_SITE_CASES = {
+    # name: (cfg, weight seed, lengths, p, mask seed)
+    "p2_d50": (dict(B=3, L=20, P=2, C=6, nlayers=2, D_t=100, D_a=100, D_v=512), 121, [20, 13, 7], 0.5, 1210),
+    "p2_d10": (dict(B=3, L=20, P=2, C=6, nlayers=2, D_t=100, D_a=100, D_v=512), 121, [20, 13, 7], 0.1, 1211),
+    "p3_d50": (dict(B=4, L=17, P=3, C=7, nlayers=3, D_t=100, D_a=100, D_v=342), 122, [17, 9, 1, 12], 0.5, 1220),
+    "p3_d10": (dict(B=4, L=17, P=3, C=7, nlayers=3, D_t=100, D_a=100, D_v=342), 122, [17, 9, 1, 12], 0.1, 1221),
+}
+DROPOUT_SITE_FULL_GRADS = ("smax_fc.weight", "graph_model.graph_net.convs.0.weight", "graph_model.graph_net.fcs.0.bias",
+                           "graph_model.graph_net.rnn.bias_ih_l0", "rnn_parties.bias_hh_l1", "linear_l.bias")
+
+
+def seeded_keep_mask(rs, shape, p):
+    """The 0 / 1 keep mask of one dropout call: kept where the next ``shape`` uniforms of ``rs`` are >= p (our own
+    convention; tests/test_dropout_sites.py draws the same way)."""
+    return torch.from_numpy((rs.random_sample(tuple(shape)) >= p).astype(np.float32))
+
+
+def export_dropout_sites(out_dir=HERE):
+    """The reference in train() with dropout = p at every site outside the GRUs (the ``dropout`` attribute of its nn.GRU
+    modules is set to 0 after construction: nn.GRU draws its inter-layer mask inside one ATen call, out of reach), with
+    torch.nn.functional.dropout replaced for the duration of the run by a function that draws each call's keep mask from
+    one RandomState in call order (that covers F.dropout and nn.Dropout alike).  Stored: the shapes the calls saw, the
+    train-mode log-probs, the loss, digests of every live gradient and a few full gradients.  One thread: the fixture is
+    regenerated bit for bit by tests/test_dropout_sites.py."""
+    import torch.nn.functional as F
+    _, _, _, ref_loss = ref_shim.modules()
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    out = {}
+    try:
+        for name, (cfg, seed, lengths, p, mseed) in DROPOUT_SITE_CASES.items():
+            batch = synthetic.make_batch(seed + 1, lengths=lengths, **cfg)
+            args = (batch["textf"], batch["qmask"], batch["umask"], batch["lengths"], batch["acouf"], batch["visuf"])
+            m = ref_model(cfg, seed, p).train()
+            for mod in m.modules():
+                if isinstance(mod, torch.nn.GRU):
+                    mod.dropout = 0.0
+            rs = np.random.RandomState(mseed)
+            shapes = []
+
+            def seeded_dropout(input, p=0.5, training=True, inplace=False):
+                if not training or p <= 0:
+                    return input
+                shapes.append(tuple(input.shape))
+                return input * seeded_keep_mask(rs, input.shape, p) * (1.0 / (1.0 - p))
+            real = F.dropout
+            F.dropout = seeded_dropout
+            try:
+                logp = m(*args)[0]
+                label = torch.cat([batch["label"][j][:n] for j, n in enumerate(batch["lengths"])])
+                loss = ref_loss.FocalLoss(gamma=0.5)(logp, label)
+                loss.backward()
+            finally:
+                F.dropout = real
+            out[name + "/site_shapes"] = np.array([list(s) for s in shapes], dtype=np.int64)
+            out[name + "/log_prob"] = logp.detach().numpy()
+            out[name + "/loss"] = np.array(loss.item(), dtype=np.float64)
+            live = []
+            for k, prm in m.named_parameters():
+                if prm.grad is not None and float(prm.grad.abs().max()) > 0:
+                    live.append(k)
+                    out[name + "/gd/" + k] = grad_digest(prm.grad)
+            out[name + "/live_params"] = np.array(live)
+            named = dict(m.named_parameters())
+            for k in DROPOUT_SITE_FULL_GRADS:
+                out[name + "/g/" + k] = named[k].grad.numpy()
+            print("dropout sites", name, "N=%d" % sum(lengths), "p", p, "loss", loss.item(), "sites", shapes, "live", len(live))
+    finally:
+        torch.set_num_threads(threads)
+    np.savez_compressed(os.path.join(out_dir, "dropout_sites.npz"), **out)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
+    if "--dropout-sites-only" in sys.argv:     # [--out DIR]: the fixture of tests/test_dropout_sites.py alone
+        export_dropout_sites(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else HERE)
+        sys.exit(0)
     if "--variants-only" in sys.argv:          # (round 5: the bimodal / av_using_lstm fixtures, without touching the others)
         export_variants()
         sys.exit(0)
@@ -428,3 +503,4 @@ if __name__ == "__main__":
     export_gcnii()
     export_e2e()
     export_train_trace()
+    export_dropout_sites()
