@@ -46,7 +46,8 @@ extern "C" {
  * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
 int64_t mmdfn_riders_bytes(void);
 
-/* Library / device sanity: returns the ABI version (currently 20: 19 + mmdfn_linear_planes_group_in (input dropout in the
+/* Library / device sanity: returns the ABI version (currently 21: 20 + the TFN tensor-fusion kernels mmdfn_tfn_{workspace,fwd,bwd_input,bwd_weight,keep_flags};
+ * 20 = 19 + mmdfn_linear_planes_group_in (input dropout in the
  * plane projection's staging step), mmdfn_linear_planes_group_party (party-ordered store) and mmdfn_linear_group_seg2 (two K segments per few-row problem); 19 = 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
  * and the LMF fusion kernels mmdfn_lmf_{fwd,bwd,bwd_width}; 18 = 17 with the rider hand-off made explicit -- the rider context
  * `riders` (mmdfn_riders_bytes) is an argument of mmdfn_wgrad_riders_{stage,staged,flush,drain}, mmdfn_keep_flags_{stage,flush},
@@ -630,6 +631,38 @@ int mmdfn_lmf_fwd(float* P, const float* factor_a, const float* factor_v, const 
                   int R, int ldp, int ldo, void* stream);
 int mmdfn_lmf_bwd(const float* g, const float* P, const float* w, float* D, int64_t N, int O, int R, int ldg, int ldp, int ldd,
                   void* stream);
+
+/* ---------------------------------------------------------------------------
+ * TFN  tensor fusion (reference model_fusion.py:169-211) after its subnets, ABI 21 (csrc/tensor_fusion.hip):
+ *   Z[n, (i V1 + j) T1 + k] = [1, h_a][n, i] [1, h_v][n, j] [1, h_t][n, k]      (A1 = Ha + 1, ..., K = A1 V1 T1)
+ *   out = act(dropout(Z) W1^T + b1),  W1 (O, K) with row stride ldw, O <= 304, act = ReLU when relu != 0.
+ * Z, its dropout mask and dZ are never stored: every kernel regenerates its fragments of dropout(Z) from the h rows ((N, H_m),
+ * row strides ldh*) and the keep flag of element (n, k), a pure function of the generator state the forward call used
+ * (csrc/tfn_keep.h: Philox counter offset + n ceil(K / 8) + k / 8, 16-bit draw k % 8 against keep * 65536).  Exact f32 products,
+ * fixed-order slab sums: the same inputs and state give the same bits.
+ *   mmdfn_tfn_workspace  floats of `workspace` for mmdfn_tfn_fwd (which = 0: K slabs of (N, O)) and mmdfn_tfn_bwd_input
+ *                        (which = 1: pair slabs of (N, A1 + V1 + T1)); -1: widths the kernels do not take.
+ *   mmdfn_tfn_fwd        state != NULL (dropout on): the keep-flag generator state of the device ((seed, offset, ...), int64);
+ *                        the call copies (seed, offset) to `used` (2 int64, kept for the backward calls) and advances the
+ *                        offset by `counters` (>= N ceil(K / 8)); keep = 1 - p, scale = 1 / keep (0 for keep = 0).
+ *                        state == NULL: no dropout (used / counters / keep / scale ignored).
+ *   mmdfn_tfn_bwd_input  dpre = dy (.) (y1 > 0) (relu != 0; y1 = the forward's out) or dy, written to dpre (N, O);
+ *                        dh_m (N, H_m) contiguous = the gradients of the three h; used == NULL: no dropout.
+ *   mmdfn_tfn_bwd_weight dW1 (O, K) contiguous = dpre^T dropout(Z), every element written once.
+ *   mmdfn_tfn_keep_flags test / debug: out (rows, K) = the 0 / 1 keep flags of rows row0 .. row0 + rows - 1 of an N-row call.
+ * ------------------------------------------------------------------------- */
+int64_t mmdfn_tfn_workspace(int64_t N, int Ha, int Hv, int Ht, int O, int which);
+int mmdfn_tfn_fwd(const float* ha, const float* hv, const float* ht, int ldha, int ldhv, int ldht, const float* W1, int64_t ldw,
+                  const float* b1, void* state, void* used, int64_t counters, float keep, float scale, float* out,
+                  float* workspace, int64_t N, int Ha, int Hv, int Ht, int O, int relu, void* stream);
+int mmdfn_tfn_bwd_input(const float* dy, const float* y1, int relu, const float* W1, int64_t ldw, const float* ha,
+                        const float* hv, const float* ht, int ldha, int ldhv, int ldht, void* used, float keep, float scale,
+                        float* dpre, float* dha, float* dhv, float* dht, float* workspace, int64_t N, int Ha, int Hv, int Ht,
+                        int O, void* stream);
+int mmdfn_tfn_bwd_weight(const float* dpre, const float* ha, const float* hv, const float* ht, int ldha, int ldhv, int ldht,
+                         void* used, float keep, float scale, float* dW1, int64_t N, int Ha, int Hv, int Ht, int O,
+                         void* stream);
+int mmdfn_tfn_keep_flags(void* used, float keep, float* out, int64_t N, int64_t K, int64_t row0, int64_t rows, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K10  FocalLoss (reference loss.py:14-34) as one launch each way:

@@ -91,6 +91,11 @@ SIGNATURES = {
     "mmdfn_lmf_bwd_width": [_I, _I],
     "mmdfn_lmf_fwd": [_P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "mmdfn_lmf_bwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "mmdfn_tfn_workspace": [_L, _I, _I, _I, _I, _I],
+    "mmdfn_tfn_fwd": [_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _L, _F, _F, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "mmdfn_tfn_bwd_input": [_P, _P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "mmdfn_tfn_bwd_weight": [_P, _P, _P, _P, _I, _I, _I, _P, _F, _F, _P, _L, _I, _I, _I, _I, _P],
+    "mmdfn_tfn_keep_flags": [_P, _F, _P, _L, _L, _L, _L, _P],
     "mmdfn_focal_loss_fwd": [_P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
     "mmdfn_focal_loss_bwd": [_P, _P, _P, _P, _L, _I, _P],
     "mmdfn_focal_loss_fwd_grad": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -112,7 +117,7 @@ SIGNATURES = {
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class HipLibraryError(RuntimeError):

@@ -1,7 +1,8 @@
 // Device side of the dropout keep-flag generator (encoder_glue.hip: see the comment there), as a function of (block, blocks,
 // threads per block), so that the draw of a step's flags can also run as RIDER workgroups of the first GRU layer's forward
 // recurrence launch (gru.hip: 96 of 256 CUs idle for 69 us at cfg2; the flags' first consumer is the dropout behind that layer).
-// A code header, included by exactly those two translation units.
+// A code header, included by exactly those two translation units -- and, for `philox4x32_10` alone, by tfn_keep.h (tensor_fusion.hip:
+// the TFN kernels draw the keep flags of the fused tensor where they use them, from the same generator stream).
 #pragma once
 #include "mmdfn_internal.h"
 

@@ -14,6 +14,10 @@
   (model.py:1394-1395).  The three subnets are one grouped launch, the 3 R products [1, h_m] . factor_m grouped launches into
   column blocks of one buffer, and the rank-weighted product over modalities one fused kernel each way (csrc/lmf.hip).
   As in the reference, ``post_fusion_dropout`` is constructed and never applied.
+* ``TFN`` (model_fusion.py:123-211): tensor fusion network, the ``tfn_only`` option of the reference's graph-free model.  The
+  three subnets are one grouped launch; the fused tensor [1, h_a] (x) [1, h_v] (x) [1, h_t] (N x 101^3 floats by default),
+  its dropout mask and its gradient are never materialised: csrc/tensor_fusion.hip generates the operand inside the three
+  products against post_fusion_layer_1's (300, 1 030 301) weight and draws the dropout flags there (``ops.tfn_fuse``).
 """
 import torch
 import torch.nn as nn
@@ -156,3 +160,30 @@ class LMF(nn.Module):
         ha, hv, ht = ops.linear_group([audio_x, video_x, text_x], [n.weight for n in nets], [n.bias for n in nets], hip=True)
         return ops.lmf_fuse(ha, hv, ht, self.audio_factor, self.video_factor, self.text_factor, self.fusion_weights,
                             self.fusion_bias)
+
+
+class TFN(nn.Module):
+    def __init__(self, input_dims=(300, 300, 300), hidden_dims=(100, 100, 100), dropouts=0.4, post_fusion_dim=300, output_dim=300):
+        super().__init__()
+        self.audio_in, self.video_in, self.text_in = input_dims
+        self.audio_hidden, self.video_hidden, self.text_hidden = hidden_dims
+        self.post_fusion_dim = post_fusion_dim
+        self.post_fusion_prob = dropouts
+        self.audio_subnet = nn.Linear(self.audio_in, self.audio_hidden)
+        self.video_subnet = nn.Linear(self.video_in, self.video_hidden)
+        self.text_subnet = nn.Linear(self.text_in, self.text_hidden)
+        self.post_fusion_dropout = nn.Dropout(p=self.post_fusion_prob)
+        self.post_fusion_layer_1 = nn.Linear((self.text_hidden + 1) * (self.video_hidden + 1) * (self.audio_hidden + 1),
+                                             self.post_fusion_dim)
+        self.post_fusion_layer_2 = nn.Linear(self.post_fusion_dim, output_dim)
+        self.last_keep_state = None      # the generator state of the latest training-mode forward (ops.tfn_keep_flags)
+
+    def forward(self, audio_x, video_x, text_x):
+        """(N, input_dims[m]) each -> (N, output_dim).  ``post_fusion_dropout.p`` is read at call time."""
+        nets = (self.audio_subnet, self.video_subnet, self.text_subnet)
+        ha, hv, ht = ops.linear_group([audio_x, video_x, text_x], [n.weight for n in nets], [n.bias for n in nets], hip=True)
+        l1, l2 = self.post_fusion_layer_1, self.post_fusion_layer_2
+        y1 = ops.tfn_fuse(ha, hv, ht, l1.weight, l1.bias, self.post_fusion_dropout.p,
+                          self.training and self.post_fusion_dropout.training)
+        self.last_keep_state = getattr(y1.grad_fn, "used_state", None)
+        return ops.linear_group([y1], [l2.weight], [l2.bias], act=1, hip=True)[0]

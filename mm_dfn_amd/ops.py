@@ -37,11 +37,11 @@ from .ops_party import (  # noqa: F401
 )
 from .ops_fusion import (  # noqa: F401
     _SoftmaxScale, softmax_scale, _MfnMem, mfn_mem, _GatedPair, gated_pair, _ResidualProducts, residual_products, _Lmf,
-    lmf_fuse,
+    lmf_fuse, _Tfn, tfn_fuse, tfn_keep_flags,
 )
 from .ops_flags import (  # noqa: F401
     _FLAG_SCOPE, _FLAG_HINT, flag_pool, keep_scale, _FLAG_STATE, _FLAG_CONSUMED, flags_consumed, flag_state_snapshot,
-    flag_state_restore, flag_state_sync, flags_advance_host, draw_flags, keep_flags, _MaskScale, mask_scale,
+    flag_state_restore, flag_state_sync, flags_advance_host, draw_flags, reserve_counters, keep_flags, _MaskScale, mask_scale,
     stage_flag_draw, finish_flag_draw,
 )
 from .ops_head import (  # noqa: F401

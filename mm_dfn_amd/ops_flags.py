@@ -175,6 +175,33 @@ def draw_flags(n, p, device, riders=None):
     return out
 
 
+def reserve_counters(counters, device):
+    """The host bookkeeping of ``draw_flags`` for a kernel that draws its flags ITSELF (ops_fusion.tfn_fuse: the flags of the
+    fused tensor are regenerated wherever they are needed and never stored): returns (device generator state, counters
+    reserved).  The kernel reads (seed, offset) there and advances the offset by exactly the returned count.  In eager mode
+    the state is first brought in line with torch's CUDA generator, whose offset is then moved past the reserved counters;
+    the tally read by ``flags_consumed`` grows by the same amount, so a captured step moves the host generator per replay."""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    ent = _FLAG_STATE.get(idx)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if ent is None:
+        if capturing:
+            raise RuntimeError("the first dropout draw on a device cannot happen inside a stream capture (run one eager step first)")
+        ent = _FLAG_STATE[idx] = [torch.zeros(4, dtype=torch.int64, device=device), None]
+    counters = 4 * ((int(counters) + 3) // 4)          # (torch's offset moves in multiples of 4)
+    if not capturing:
+        gen = torch.cuda.default_generators[idx]
+        now = (int(gen.initial_seed()), int(gen.get_offset()))
+        if ent[1] != now:
+            seed = now[0] - (1 << 64) if now[0] >= (1 << 63) else now[0]
+            ent[0].copy_(torch.tensor([seed, now[1], 0, 0], dtype=torch.int64), non_blocking=False)
+        gen.set_offset(now[1] + counters)
+        ent[1] = (now[0], int(gen.get_offset()))
+    _FLAG_CONSUMED[idx] = _FLAG_CONSUMED.get(idx, 0) + counters
+    return ent[0], counters
+
+
 def keep_flags(n, p, device, site=None):
     """n fp32 keep flags (1 with probability 1 - p), 16-byte aligned.  ``site``: the caller's label for the test tap."""
     out = _keep_flags(int(n), p, device)

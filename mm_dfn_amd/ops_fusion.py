@@ -1,4 +1,4 @@
-"""Kernels of the fusion modules (MFN, MMGatedAttention, LMF) and of the graph-free model's per-modality products.
+"""Kernels of the fusion modules (MFN, MMGatedAttention, LMF, TFN) and of the graph-free model's per-modality products.
 
 Part of the operator layer over the C-ABI kernels (libmmdfn_hip.so); `mm_dfn_amd.ops` re-exports every name.
 Every function launches hand-written gfx950 kernels on the current HIP stream; there is no CPU / eager fallback.
@@ -6,6 +6,7 @@ Every function launches hand-written gfx950 kernels on the current HIP stream; t
 import torch
 
 from . import _hip
+from .ops_flags import keep_scale, reserve_counters
 from .ops_linear import linear_group_raw
 from .ops_pad import weight_operand
 from .ops_wgrad import _wgrad, colsum, gemm_tn_grouped
@@ -209,3 +210,100 @@ class _Lmf(torch.autograd.Function):
 def lmf_fuse(ha, hv, ht, fa, fv, ft, w, bias):
     """(N, O) = sum_r w[0, r] prod_m ([1, h_m] . factor_m[r]) + bias (see _Lmf)."""
     return _Lmf.apply(ha, hv, ht, fa, fv, ft, w, bias)
+
+
+def _tfn_rows(h):
+    """(N, H) fp32 rows with unit inner stride (a column slice of a wider matrix is read in place)."""
+    return h if h.stride(1) == 1 and h.stride(0) >= h.shape[1] else h.contiguous()
+
+
+def _tfn_workspace(lib, N, H, O, which, device):
+    n = int(lib.mmdfn_tfn_workspace(N, H[0], H[1], H[2], O, which))
+    if n < 0:
+        raise ValueError("tfn_fuse: hidden widths %s with %d outputs are not taken by the kernels (at most 304 outputs; the three "
+                         "[1, h] rows of 64 utterances must fit the LDS next to a weight tile)" % (tuple(H), O))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+class _Tfn(torch.autograd.Function):
+    """Tensor fusion of TFN (reference model_fusion.py:189-206) after its subnets: out = act(dropout_p(Z) W1^T + b1) with
+    Z[n, (i V1 + j) T1 + k] = [1, h_a][n, i] [1, h_v][n, j] [1, h_t][n, k].  Neither Z nor its dropout mask nor dZ exists:
+    csrc/tensor_fusion.hip regenerates the fragments it needs in each of the three products (forward, dW1, dh_m), the keep
+    flags as a function of the generator state the forward call read (saved as a 2-word device tensor) and the element's
+    position.  Backward returns dh_a, dh_v, dh_t, dW1, db1 to autograd."""
+
+    @staticmethod
+    def forward(ctx, ha, hv, ht, W1, b1, p, training, relu):
+        _hip.require_cuda(ha, hv, ht, W1, b1)
+        _hip.require_f32(ha, hv, ht, W1, b1)
+        if any(h.dim() != 2 or h.shape[0] != ha.shape[0] or h.shape[1] < 1 for h in (ha, hv, ht)) or ha.shape[0] < 1:
+            raise ValueError("tfn_fuse: ha, hv, ht must be (N, H_m) matrices with the same N >= 1")
+        hs = [_tfn_rows(h) for h in (ha, hv, ht)]
+        N, H = hs[0].shape[0], [h.shape[1] for h in hs]
+        K = (H[0] + 1) * (H[1] + 1) * (H[2] + 1)
+        if W1.dim() != 2 or W1.shape[1] != K or b1.shape != (W1.shape[0],):
+            raise ValueError("tfn_fuse: W1 must be (O, %d) and b1 (O,)" % K)
+        O = W1.shape[0]
+        if W1.stride(1) != 1 or W1.stride(0) < K:
+            W1 = W1.contiguous()
+        b1 = b1.contiguous()
+        p = float(p)
+        lib = _hip.lib()
+        ws = _tfn_workspace(lib, N, H, O, 0, ha.device)
+        drop = bool(training) and p > 0.0
+        used = state = None
+        counters = 0
+        if drop:
+            state, counters = reserve_counters(N * ((K + 7) // 8), ha.device)
+            used = torch.empty(2, dtype=torch.int64, device=ha.device)
+        keep = max(0.0, 1.0 - p) if drop else 1.0
+        scale = keep_scale(p) if drop else 1.0
+        out = torch.empty(N, O, dtype=torch.float32, device=ha.device)
+        _hip.check(lib.mmdfn_tfn_fwd(_hip.ptr(hs[0]), _hip.ptr(hs[1]), _hip.ptr(hs[2]), hs[0].stride(0), hs[1].stride(0),
+                                     hs[2].stride(0), _hip.ptr(W1), W1.stride(0), _hip.ptr(b1), _hip.ptr(state), _hip.ptr(used),
+                                     counters, keep, scale, _hip.ptr(out), _hip.ptr(ws), N, H[0], H[1], H[2], O, int(bool(relu)),
+                                     _hip.stream()), "mmdfn_tfn_fwd")
+        ctx.keep, ctx.scale, ctx.relu, ctx.drop = keep, scale, bool(relu), drop
+        ctx.save_for_backward(hs[0], hs[1], hs[2], W1, out if relu else None, used)
+        ctx.used_state = used                        # (tests: the flags of this call through ops.tfn_keep_flags)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        ha, hv, ht, W1, y1, used = ctx.saved_tensors
+        N, H, O, K = ha.shape[0], [ha.shape[1], hv.shape[1], ht.shape[1]], W1.shape[0], W1.shape[1]
+        dy = dy.contiguous()
+        lib = _hip.lib()
+        ws = _tfn_workspace(lib, N, H, O, 1, dy.device)
+        dpre = torch.empty(N, O, dtype=torch.float32, device=dy.device)
+        dhs = [torch.empty(N, h, dtype=torch.float32, device=dy.device) for h in H]
+        _hip.check(lib.mmdfn_tfn_bwd_input(_hip.ptr(dy), _hip.ptr(y1), int(ctx.relu), _hip.ptr(W1), W1.stride(0), _hip.ptr(ha),
+                                           _hip.ptr(hv), _hip.ptr(ht), ha.stride(0), hv.stride(0), ht.stride(0), _hip.ptr(used),
+                                           ctx.keep, ctx.scale, _hip.ptr(dpre), _hip.ptr(dhs[0]), _hip.ptr(dhs[1]),
+                                           _hip.ptr(dhs[2]), _hip.ptr(ws), N, H[0], H[1], H[2], O, _hip.stream()),
+                   "mmdfn_tfn_bwd_input")
+        dW1 = db1 = None
+        if ctx.needs_input_grad[3]:
+            dW1 = torch.empty(O, K, dtype=torch.float32, device=dy.device)
+            _hip.check(lib.mmdfn_tfn_bwd_weight(_hip.ptr(dpre), _hip.ptr(ha), _hip.ptr(hv), _hip.ptr(ht), ha.stride(0),
+                                                hv.stride(0), ht.stride(0), _hip.ptr(used), ctx.keep, ctx.scale, _hip.ptr(dW1), N,
+                                                H[0], H[1], H[2], O, _hip.stream()), "mmdfn_tfn_bwd_weight")
+        if ctx.needs_input_grad[4]:
+            db1 = colsum(dpre)
+        return dhs[0], dhs[1], dhs[2], dW1, db1, None, None, None
+
+
+def tfn_fuse(ha, hv, ht, W1, b1, p, training, relu=True):
+    """(N, O) = act(dropout_p([1, h_a] (x) [1, h_v] (x) [1, h_t]) W1^T + b1), act = ReLU unless ``relu`` is False; the dropout
+    (training mode, p > 0) draws from the package's keep-flag generator inside the kernels (see _Tfn)."""
+    return _Tfn.apply(ha, hv, ht, W1, b1, p, training, relu)
+
+
+def tfn_keep_flags(used_state, N, K, p, row0, rows):
+    """Test / debug: the (rows, K) 0 / 1 keep flags that a training-mode ``tfn_fuse`` call of N rows whose generator state
+    was ``used_state`` (2 int64 on the device: the tensor the call saved) applies to rows row0 .. row0 + rows - 1."""
+    _hip.require_cuda(used_state)
+    out = torch.empty(int(rows), int(K), dtype=torch.float32, device=used_state.device)
+    _hip.check(_hip.lib().mmdfn_tfn_keep_flags(_hip.ptr(used_state), max(0.0, 1.0 - float(p)), _hip.ptr(out), int(N), int(K),
+                                               int(row0), int(rows), _hip.stream()), "mmdfn_tfn_keep_flags")
+    return out

@@ -243,6 +243,20 @@ def _linear_dx(dy2, weight):
     return dense_kn(dy2, weight)
 
 
+def _dx_problem(dy2, wk):
+    """dX = dY . W as a K-major problem of the few-row kernel; an output width N that is no multiple of 4 (TFN's subnets with
+    odd hidden widths) contracts over zero-padded copies of both operands (the extra terms are 0 * 0)."""
+    n = dy2.shape[1]
+    if n % 4 == 0:
+        return dict(x=dy2, wk=wk)
+    npad = (n + 3) & ~3
+    d = dy2.new_zeros(dy2.shape[0], npad)
+    d[:, :n].copy_(dy2)
+    w = wk.new_zeros(npad, wk.shape[1])
+    w[:n].copy_(wk)
+    return dict(x=d, wk=w)
+
+
 class _LinearGroup(torch.autograd.Function):
     """n independent projections y_g = act(x_g W_g^T + b_g) that become available together (the three modality
     projections model.py:1065,1094,1129; the hoisted input contractions of the context and the party GRU).  Forward
@@ -294,7 +308,7 @@ class _LinearGroup(torch.autograd.Function):
             # input gradients dX_g = dY_g . W_g of the whole group in one launch: the weight is read as stored ((N, K) = the
             # K-major form of the product over N)
             need = [g for g in range(n) if ctx.needs_input_grad[2 + g]]
-            outs = linear_group_raw([dict(x=dy2s[g], wk=weight_operand(sv[3 * g + 1])) for g in need]) if need else []
+            outs = linear_group_raw([_dx_problem(dy2s[g], weight_operand(sv[3 * g + 1])) for g in need]) if need else []
             dxs = [None] * n
             for g, o in zip(need, outs):
                 K = sv[3 * g + 1].shape[1]
