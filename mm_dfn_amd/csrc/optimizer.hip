@@ -49,8 +49,10 @@ __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict_
 extern "C" int mmdfn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                                float beta2, float eps, float weight_decay, int step, void* stream) {
     if (n <= 0 || step < 1) return -1;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    // bias corrections in double, rounded once: a float beta2^t next to 1 carries half an ulp of 1, which 1 - x magnifies by
+    // 1 / (1 - beta2^t) -- about 100 u on the update at steps 2..5 with beta2 = 0.999 (tests/test_loss_optimizer_kernels_gpu.py)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;

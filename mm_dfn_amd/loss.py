@@ -131,4 +131,6 @@ class FocalLoss(nn.Module):
                 self.alpha = self.alpha.to(device=input.device, dtype=input.dtype)
             logpt = logpt * self.alpha.gather(0, target.view(-1))
         loss = -1 * (1 - pt) ** self.gamma * logpt
+        if self.ignore_index is not None and loss.numel() == 0:
+            return loss.sum()            # every row left out: 0 with zero gradients, as the device form (not the NaN of an empty mean)
         return loss.mean() if self.size_average else loss.sum()

@@ -12,10 +12,19 @@ from .ops_pad import weight_operand
 from .ops_wgrad import _wgrad, colsum, gemm_tn_grouped
 
 _GROUP = 8          # problems per grouped launch (linear_small.hip SG_MAX, gemm_tn.hip TN_MAXG)
+_LMF_RANK_MAX = 8   # csrc/lmf.hip LMF_RMAX
+_COLSUM_COLS = 4096 # columns per column-sum launch (csrc/encoder_glue.hip mmdfn_colsum: 64 blocks of 64 columns)
 
 
 def _chunks(xs):
     return [xs[i:i + _GROUP] for i in range(0, len(xs), _GROUP)]
+
+
+def _colsum_wide(D):
+    """colsum of a matrix of any width (a multiple of 4): one launch per 4096 columns, each on its column block in place."""
+    if D.shape[1] <= _COLSUM_COLS:
+        return colsum(D)
+    return torch.cat([colsum(D[:, i:i + _COLSUM_COLS]) for i in range(0, D.shape[1], _COLSUM_COLS)])
 
 
 class _SoftmaxScale(torch.autograd.Function):
@@ -154,9 +163,9 @@ class _Lmf(torch.autograd.Function):
     """Low-rank fusion of LMF (reference model_fusion.py:274-310) after its subnets:
     out = sum_r w_r prod_m ([1, h_m] . factor_m[r]) + bias, modalities a, v, t.  The 3 R products h_m . factor_m[r, 1:, :]
     are grouped launches of the few-row kernel into column blocks of one (N, 3 R O) buffer P; csrc/lmf.hip adds the constant
-    rows and forms the rank-weighted product.  Backward: csrc/lmf.hip writes [dP | g | T], one column-sum launch gives
-    d factor_m[r, 0, :], d bias and d w, grouped gemm_tn launches give d factor_m[r, 1:, :] = h_m^T dP_m,r, and R accumulating
-    grouped launches give dh_m = sum_r dP_m,r factor_m[r, 1:, :]^T."""
+    rows and forms the rank-weighted product.  Backward: csrc/lmf.hip writes [dP | g | T], one column-sum launch per 4096
+    columns of it gives d factor_m[r, 0, :], d bias and d w, grouped gemm_tn launches give d factor_m[r, 1:, :] = h_m^T dP_m,r,
+    and R accumulating grouped launches give dh_m = sum_r dP_m,r factor_m[r, 1:, :]^T."""
 
     @staticmethod
     def forward(ctx, ha, hv, ht, fa, fv, ft, w, bias):
@@ -165,6 +174,8 @@ class _Lmf(torch.autograd.Function):
         _hip.require_f32(*hs, *fs, w, bias)
         fs = tuple(f.contiguous() for f in fs)
         R, O, N = fs[0].shape[0], fs[0].shape[2], hs[0].shape[0]
+        if not 1 <= R <= _LMF_RANK_MAX:
+            raise ValueError("lmf_fuse: rank %d is outside the kernels' range 1..%d" % (R, _LMF_RANK_MAX))
         if O % 4 or any(h.shape[1] % 4 for h in hs):
             raise ValueError("lmf_fuse: output and hidden widths must be multiples of 4")
         P = torch.empty(N, 3 * R * O, dtype=torch.float32, device=hs[0].device)
@@ -191,7 +202,7 @@ class _Lmf(torch.autograd.Function):
         D = torch.empty(N, width, dtype=torch.float32, device=P.device)
         _hip.check(lib.mmdfn_lmf_bwd(_hip.ptr(g), _hip.ptr(P), _hip.ptr(w), _hip.ptr(D), N, O, R, g.stride(0), P.stride(0),
                                      D.stride(0), _hip.stream()), "mmdfn_lmf_bwd")
-        sums = colsum(D)
+        sums = _colsum_wide(D)       # (rank 5 and up at the default 300 outputs: more than one launch's 4096 columns)
         blk = lambda m, r: D[:, (m * R + r) * O:(m * R + r + 1) * O]
         dfs = [torch.empty_like(f) for f in fs]
         for m in range(3):

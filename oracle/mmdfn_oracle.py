@@ -409,14 +409,64 @@ def gcnii_deep(x, dia_len, params, prefix, nlayers, lamda=0.5, alpha=0.1, dropou
     return torch.cat([x, cur], -1) if use_residue else cur
 
 
-def gated_attention_general(a, v, l, params, prefix="gatedatt."):
-    """MMGatedAttention.forward, att_type='general', three modalities, eval (model.py:761-781)."""
+def gated_attention_general(a, v, l, params, prefix="gatedatt.", modals="avl"):
+    """MMGatedAttention.forward, att_type='general', eval (model.py:761-781).  ``modals``: 'avl' (the three pair blocks
+    av | al | vl concatenated) or a two-modality set 'av', 'al', 'vl' (that pair's block alone; the absent input is unused)."""
     lin = lambda name, t: F.linear(t, params[prefix + name + ".weight"], params.get(prefix + name + ".bias"))
-    ha, hv, hl = torch.tanh(lin("transform_a", a)), torch.tanh(lin("transform_v", v)), torch.tanh(lin("transform_l", l))
-    z_av = torch.sigmoid(lin("transform_av", torch.cat([a, v, a * v], -1)))
-    z_al = torch.sigmoid(lin("transform_al", torch.cat([a, l, a * l], -1)))
-    z_vl = torch.sigmoid(lin("transform_vl", torch.cat([v, l, v * l], -1)))
-    return torch.cat([z_av * ha + (1 - z_av) * hv, z_al * ha + (1 - z_al) * hl, z_vl * hv + (1 - z_vl) * hl], -1)
+    x = {"a": a, "v": v, "l": l}
+    use = [m for m in "avl" if m in modals]
+    if len(use) < 2:
+        raise ValueError("gated_attention_general: at least two modalities")
+    h = {m: torch.tanh(lin("transform_" + m, x[m])) for m in use}
+    out = []
+    for m, n in (("a", "v"), ("a", "l"), ("v", "l")):
+        if m in use and n in use:
+            z = torch.sigmoid(lin("transform_" + m + n, torch.cat([x[m], x[n], x[m] * x[n]], -1)))
+            out.append(z * h[m] + (1 - z) * h[n])
+    return out[0] if len(out) == 1 else torch.cat(out, -1)
+
+
+def mfn(x, params, prefix=""):
+    """MFN.forward in eval mode (model_fusion.py:62-120).  x: (T, n, d_l + d_a + d_v), split l | a | v in that order;
+    returns (T, n, 3 dh + mem_dim) = [h_l | h_a | h_v | mem].  Dtype-generic (runs in the dtype of x / params)."""
+    P = lambda k: params[prefix + k]
+    lin = lambda name, t: F.linear(t, P(name + ".weight"), P(name + ".bias"))
+    mlp = lambda name, t: lin(name + "_fc2", torch.relu(lin(name + "_fc1", t)))
+    T, n = x.shape[0], x.shape[1]
+    names = ("lstm_l", "lstm_a", "lstm_v")
+    d = [P(k + ".weight_ih").shape[1] for k in names]
+    dh = [P(k + ".weight_hh").shape[1] for k in names]
+    xs = torch.split(x, d, dim=2)
+    h = [x.new_zeros(n, k) for k in dh]
+    c = [x.new_zeros(n, k) for k in dh]
+    mem = x.new_zeros(n, P("att2_fc2.weight").shape[0])
+    rows = []
+    for t in range(T):
+        prev_cs = torch.cat(c, 1)
+        new = [lstm_cell(xs[m][t], h[m], c[m], P(k + ".weight_ih"), P(k + ".weight_hh"), P(k + ".bias_ih"), P(k + ".bias_hh"))
+               for m, k in enumerate(names)]
+        h, c = [hc[0] for hc in new], [hc[1] for hc in new]
+        c_star = torch.cat([prev_cs, torch.cat(c, 1)], 1)
+        attended = torch.softmax(mlp("att1", c_star), 1) * c_star
+        c_hat = torch.tanh(mlp("att2", attended))
+        both = torch.cat([attended, mem], 1)
+        mem = torch.sigmoid(mlp("gamma1", both)) * mem + torch.sigmoid(mlp("gamma2", both)) * c_hat
+        rows.append(torch.cat(h + [mem], 1))
+    return torch.stack(rows)
+
+
+def lmf(xs, params, prefix=""):
+    """LMF.forward (model_fusion.py:274-310; its post-fusion dropout is never applied).  xs = (audio, video, text), each
+    (N, input_dim); returns (N, output_dim).  Dtype-generic."""
+    P = lambda k: params[prefix + k]
+    zy = None
+    for x, m in zip(xs, ("audio", "video", "text")):
+        h = F.linear(x, P(m + "_subnet.weight"), P(m + "_subnet.bias"))
+        h1 = torch.cat([torch.ones(h.shape[0], 1, dtype=h.dtype, device=h.device), h], 1)
+        p = torch.matmul(h1, P(m + "_factor"))                      # (rank, N, O)
+        zy = p if zy is None else zy * p
+    out = torch.matmul(P("fusion_weights"), zy.permute(1, 0, 2)).squeeze() + P("fusion_bias")
+    return out.view(-1, P("fusion_bias").shape[-1])
 
 
 def forward_deepgcn(params, U, qmask, umask, lengths, U_a, U_v, cfg, training=False, engine="manual",

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import mmdfn_oracle as O
 from mm_dfn_amd import FocalLoss, ops, train
 from mm_dfn_amd.fusion import LMF
 from test_fusion_baselines import CASES, build
@@ -51,20 +52,6 @@ def test_fusion_baselines_against_reference_goldens(name):
             assert gr is None or float(gr.abs().max()) == 0.0, k
 
 
-def _lmf_f64(mod, xs):
-    """The reference's LMF forward (model_fusion.py:274-310) in float64."""
-    nets = (mod.audio_subnet, mod.video_subnet, mod.text_subnet)
-    facs = (mod.audio_factor, mod.video_factor, mod.text_factor)
-    zy = None
-    for x, net, f in zip(xs, nets, facs):
-        h = x @ net.weight.double().t() + net.bias.double()
-        h1 = torch.cat([torch.ones(h.shape[0], 1, dtype=h.dtype, device=h.device), h], 1)
-        p = torch.matmul(h1, f.double())
-        zy = p if zy is None else zy * p
-    out = torch.matmul(mod.fusion_weights.double(), zy.permute(1, 0, 2)).squeeze() + mod.fusion_bias.double()
-    return out.view(-1, mod.output_dim)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [1, 37, 300])
 def test_lmf_kernels_against_float64(N):
@@ -83,7 +70,7 @@ def test_lmf_kernels_against_float64(N):
     ref = LMF().to(DEV).double()
     ref.load_state_dict({k: v.double() for k, v in mod.state_dict().items()})
     xd = [x.detach().double().requires_grad_(True) for x in xs]
-    want_out = _lmf_f64(ref, xd)
+    want_out = O.lmf(xd, dict(ref.named_parameters()))
     (want_out * G).sum().backward()
     want = [x.grad for x in xd] + [p.grad for p in ref.parameters()]
     assert (out.double() - want_out).abs().max() / want_out.abs().max() < 1e-5

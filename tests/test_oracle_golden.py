@@ -214,3 +214,31 @@ def test_graph_convolution_against_reference_golden():
     adj = adj / adj.sum(1, keepdim=True)
     for l in (1, 2, 16):
         assert np.abs(O.graph_convolution(x, adj, h0, 0.5, 0.2, l, w).numpy() - g["gconv_l%d" % l]).max() < 1e-5
+
+
+def test_mfn_and_two_modality_gated_attention():
+    """O.mfn and the two-modality form of O.gated_attention_general against the reference modules' fixtures
+    (tests/golden/fusion_modules.npz, tests/golden/make_golden.py export_fusion_modules), in float64 on the seeds and inputs of
+    test_model_gpu.test_mfn_and_gated_attention_modules_against_reference_golden.  The fixtures are float32 results, so the
+    bounds are that test's (MFN) and its 2e-6 (gated)."""
+    from mm_dfn_amd import MFN, MMGatedAttention
+    g = load("fusion_modules.npz")
+    rs = np.random.RandomState(700)
+    params = {k: v.double().requires_grad_(True) for k, v in synthetic.seeded_state_dict(MFN().state_dict(), 700).items()}
+    x = torch.from_numpy(rs.randn(9, 2, 900).astype(np.float32)).double().requires_grad_(True)
+    R = torch.from_numpy(rs.randn(9, 2, 400).astype(np.float32)).double()
+    y = O.mfn(x, params)
+    (y * R).sum().backward()
+    assert np.abs(y.detach().numpy() - g["mfn_y"]).max() < 1e-5
+    assert np.abs(x.grad.numpy() - g["mfn_dx"]).max() / np.abs(g["mfn_dx"]).max() < 1e-4
+    assert np.abs(params["gamma1_fc1.weight"].grad.numpy() - g["mfn_dW"]).max() / np.abs(g["mfn_dW"]).max() < 1e-4
+    assert all(params[k].grad is None for k in params if k.startswith(("out_fc1.", "out_fc2.")))
+    gp = {k: v.double() for k, v in synthetic.seeded_state_dict(MMGatedAttention(300, 100).state_dict(), 701).items()}
+    a, v, l = (torch.from_numpy(rs.randn(11, 300).astype(np.float32)).double() for _ in range(3))
+    assert np.abs(O.gated_attention_general(a, v, l, gp, prefix="").numpy() - g["gated_avl"]).max() < 2e-6
+    al = O.gated_attention_general(a, v, l, gp, prefix="", modals="al")
+    assert tuple(al.shape) == (11, 100) and np.abs(al.numpy() - g["gated_al"]).max() < 2e-6
+    # the pair blocks of the three-modality output are the two-modality outputs, in the order av | al | vl
+    avl = O.gated_attention_general(a, v, l, gp, prefix="")
+    for i, pair in enumerate(("av", "al", "vl")):
+        assert torch.equal(O.gated_attention_general(a, v, l, gp, prefix="", modals=pair), avl[:, 100 * i:100 * (i + 1)])
