@@ -12,8 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(256) void softmax_scale_bwd_kernel(const float* __r
 __global__ void mfn_mem_fwd_kernel(const float* __restrict__ u, const float* __restrict__ v1, const float* __restrict__ v2,
                                    const float* __restrict__ mem, float* __restrict__ out, float* __restrict__ saved, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float ch = tanhf(u[i]), g1 = sigm(v1[i]), g2 = sigm(v2[i]);
+        const float ch = tanhf(u[i]), g1 = sigmoid_exact(v1[i]), g2 = sigmoid_exact(v2[i]);
         out[i] = g1 * mem[i] + g2 * ch;
         saved[i] = ch;
         saved[n + i] = g1;
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(256) void gated_pair_fwd_kernel(const float* __rest
     float s = 0.f;
     for (int j = lane; j < D; j += 64) s += w[j] * a[j] + w[D + j] * v[j] + w[2 * D + j] * (a[j] * v[j]);
     s = wave_sum(s) + b[0];
-    const float z = sigm(s);
+    const float z = sigmoid_exact(s);
     if (lane == 0) zs[row] = z;
     for (int j = lane; j < C; j += 64)
         out[(int64_t)row * C + j] = z * tanhf(pm[(int64_t)row * C + j]) + (1.0f - z) * tanhf(pn[(int64_t)row * C + j]);

@@ -9,11 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // G: (R, 4H) pre-activations, gate order i, f, g, o.  c_prev may be null (zero state).
 __global__ void lstm_pointwise_fwd_kernel(const float* __restrict__ G, const float* __restrict__ c_prev,
                                           float* __restrict__ h_out, float* __restrict__ c_out, int64_t R, int H) {
@@ -30,9 +25,9 @@ __global__ void lstm_pointwise_fwd_kernel(const float* __restrict__ G, const flo
         float4 c, h;
 #define LSTM1(F)                                          \
     {                                                     \
-        const float cc = sigm(gf.F) * cp.F + sigm(gi.F) * tanhf(gg.F); \
+        const float cc = sigmoid_exact(gf.F) * cp.F + sigmoid_exact(gi.F) * tanhf(gg.F); \
         c.F = cc;                                         \
-        h.F = sigm(go.F) * tanhf(cc);                     \
+        h.F = sigmoid_exact(go.F) * tanhf(cc);                     \
     }
         LSTM1(x) LSTM1(y) LSTM1(z) LSTM1(w)
 #undef LSTM1
@@ -62,7 +57,7 @@ __global__ void lstm_pointwise_bwd_kernel(const float* __restrict__ G, const flo
         float4 di, df, dg, dO, dcp;
 #define LSTM1(F)                                                     \
     {                                                                \
-        const float i = sigm(gi.F), f = sigm(gf.F), gt = tanhf(gg.F), o = sigm(go.F); \
+        const float i = sigmoid_exact(gi.F), f = sigmoid_exact(gf.F), gt = tanhf(gg.F), o = sigmoid_exact(go.F); \
         const float tc = tanhf(cn.F);                                \
         const float dc = dcn.F + dhv.F * o * (1.0f - tc * tc);       \
         dO.F = dhv.F * tc * o * (1.0f - o);                          \

@@ -36,19 +36,12 @@ namespace {
 
 constexpr int RB = 16;   // rows per block
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 one4() { return make_float4(1.f, 1.f, 1.f, 1.f); }
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 __device__ __forceinline__ float4 scl4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 fma4(float4 a, float s, float4 b) { return make_float4(a.x * s + b.x, a.y * s + b.y, a.z * s + b.z, a.w * s + b.w); }
-// Gate non-linearities on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1 ulp each), as in gru.hip: the
-// accurate libm expf / tanhf are ~60-100 instructions each and the LSTM cell evaluates six per element -- more issue
-// slots than the contraction next to it.  Absolute error < 3e-7 (parity budget of the stack: 1e-5).
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // Conflict-free 16-byte fragment reads.  A wave's ds_read_b128 is serviced in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19,
 // 28-31} (+32): half of a group comes from k-group g, the other half from g + 1, so with lane (i, g) reading row i, 16-byte unit
@@ -894,7 +887,7 @@ __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(const float* __restr
             float2 gi, gf, gg, go, cn, hn;
 #define K8F(F_)                                                                 \
     {                                                                           \
-        gi.F_ = sigm(pi.F_ + bi.F_); gf.F_ = sigm(pf.F_ + bf.F_); gg.F_ = tanhf_(pg.F_ + bg.F_); go.F_ = sigm(po.F_ + bo.F_); \
+        gi.F_ = sigmoidf_(pi.F_ + bi.F_); gf.F_ = sigmoidf_(pf.F_ + bf.F_); gg.F_ = tanhf_(pg.F_ + bg.F_); go.F_ = sigmoidf_(po.F_ + bo.F_); \
         cn.F_ = gf.F_ * cp.F_ + gi.F_ * gg.F_;                                  \
         hn.F_ = go.F_ * tanhf_(cn.F_);                                          \
     }
@@ -1375,7 +1368,7 @@ __global__ __launch_bounds__(512) void lstm_gate_fwd_ws_kernel(const float* __re
         float2 gi, gf, gg, go, cn, hn;
 #define K8F(F_)                                                                 \
     {                                                                           \
-        gi.F_ = sigm(pi.F_ + bi.F_); gf.F_ = sigm(pf.F_ + bf.F_); gg.F_ = tanhf_(pg.F_ + bg.F_); go.F_ = sigm(po.F_ + bo.F_); \
+        gi.F_ = sigmoidf_(pi.F_ + bi.F_); gf.F_ = sigmoidf_(pf.F_ + bf.F_); gg.F_ = tanhf_(pg.F_ + bg.F_); go.F_ = sigmoidf_(po.F_ + bo.F_); \
         cn.F_ = gf.F_ * cp.F_ + gi.F_ * gg.F_;                                  \
         hn.F_ = go.F_ * tanhf_(cn.F_);                                          \
     }

@@ -1,7 +1,6 @@
 // Weight-gradient contraction  C (M x N) = A^T B  on the bf16 matrix path: the batch form of gemm_tn.hip (every dW = dY^T X of a
-// training step in one launch: autograd of nn.Linear / nn.GRU / nn.LSTM in the reference) with each fp32 operand cut exactly
-// into three bf16 pieces and the six piece products of weight >= 2^-16 issued as v_mfma_f32_16x16x32_bf16 (fp32-level error,
-// see propagate_split.hip for the arithmetic) instead of exact-f32 16x16x4 MFMAs (1/16 of the bf16 rate).
+// training step in one launch: autograd of nn.Linear / nn.GRU / nn.LSTM in the reference) on the six piece products of
+// bf16_pieces.h as v_mfma_f32_16x16x32_bf16 (fp32-level error) instead of exact-f32 16x16x4 MFMAs (1/16 of the bf16 rate).
 //
 // The contraction index is the ROW index r of both operands, i.e. both are k-major: an MFMA fragment (8 consecutive k of one
 // column) is a column walk through memory.  So the operands are transposed on chip:

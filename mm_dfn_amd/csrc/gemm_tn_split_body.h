@@ -3,16 +3,10 @@
 // recurrence occupies one CU per sequence and leaves the other CUs idle for its whole duration).  A code header, included by
 // exactly those two translation units.
 #pragma once
-#include "mmdfn_internal.h"
+#include "bf16_pieces.h"
 #include <type_traits>
 
 namespace tnsb {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define LDS_AS(T, p) ((__attribute__((address_space(3))) T*)(p))
 
 constexpr int SK = MMDFN_TNS_BK;          // rows per chunk = K of one MFMA step
 constexpr int TSM = MMDFN_TNS_TM;         // 128 output rows: 4 waves x 32
@@ -24,29 +18,11 @@ constexpr int IMG_B = 3 * PLANE_B;        // the three planes of one operand
 constexpr int STAGE_B = 2 * IMG_B;        // A image, B image: 55 296
 constexpr int LDS_B = 2 * STAGE_B;        // one stage per group: 110 592
 
-__device__ __forceinline__ float as_f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-// four consecutive columns of one row -> their three bf16 pieces (leading 8, next 8, next 8 significant bits, cut by
-// truncation: x = p1 + p2 + p3 + O(2^-24 x), every piece exactly representable), packed in column order
-__device__ __forceinline__ void cut4(float4 v, uint32_t himask, u32x2& p1, u32x2& p2, u32x2& p3) {
-    float x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
-    p1 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-    x0 -= as_f(as_u(x0) & himask); x1 -= as_f(as_u(x1) & himask); x2 -= as_f(as_u(x2) & himask); x3 -= as_f(as_u(x3) & himask);
-    p2 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-    x0 -= as_f(as_u(x0) & himask); x1 -= as_f(as_u(x1) & himask); x2 -= as_f(as_u(x2) & himask); x3 -= as_f(as_u(x3) & himask);
-    p3 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-}
-
 __device__ __forceinline__ u32x4 tr_frag(uint32_t addr) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_AS(s16x4, (uintptr_t)addr));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_AS(s16x4, (uintptr_t)(addr + 16 * ROWB)));
     const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
     return u32x4{l2.x, l2.y, h2.x, h2.y};
-}
-
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // ---- the 128 x 224 form (round 5) --------------------------------------------------------------------------------------------
@@ -163,7 +139,7 @@ __device__ __forceinline__ void tns_wide_body(const SQ& sq, const int p, const i
             }
             if (colpart) { cs.x += xa.x; cs.y += xa.y; cs.z += xa.z; cs.w += xa.w; }
             u32x2 a1, a2, a3;
-            cut4(xa, himask, a1, a2, a3);
+            cut4(xa.x, xa.y, xa.z, xa.w, himask, a1, a2, a3);
             const uint32_t d = wra + e * 16 * ROWB;
             *LDS_AS(u32x2, (uintptr_t)d) = a1;
             *LDS_AS(u32x2, (uintptr_t)(d + PLANE_B)) = a2;
@@ -178,7 +154,7 @@ __device__ __forceinline__ void tns_wide_body(const SQ& sq, const int p, const i
                 xb = make_float4(bok ? xb.x : 0.f, bok ? xb.y : 0.f, bok ? xb.z : 0.f, bok ? xb.w : 0.f);
             }
             u32x2 b1, b2, b3;
-            cut4(xb, himask, b1, b2, b3);
+            cut4(xb.x, xb.y, xb.z, xb.w, himask, b1, b2, b3);
             const uint32_t d = wrb + e * 8 * ROWB_W;
             *LDS_AS(u32x2, (uintptr_t)d) = b1;
             *LDS_AS(u32x2, (uintptr_t)(d + PLANE_W)) = b2;
@@ -218,7 +194,7 @@ __device__ __forceinline__ void tns_wide_body(const SQ& sq, const int p, const i
 #pragma unroll
             for (int j = 0; j < NL; ++j)
 #pragma unroll
-                for (int i = 0; i < NTM; ++i) acc[i][j] = mfma16(af[i][ai], bf[bi][j], acc[i][j]);
+                for (int i = 0; i < NTM; ++i) acc[i][j] = mfma_bf16_16(af[i][ai], bf[bi][j], acc[i][j]);
         }
     };
     auto mma_nl = [&](auto ntm_tag) {
@@ -394,8 +370,8 @@ __device__ __forceinline__ void tns_block(const SQ& sq, const int bid, unsigned 
                 a1 = u32x2{as_u(xa.x), as_u(xa.y)}; a2 = u32x2{as_u(xa.z), as_u(xa.w)}; a3 = a1;
                 b1 = u32x2{as_u(xb.x), as_u(xb.y)}; b2 = u32x2{as_u(xb.z), as_u(xb.w)}; b3 = b1;
             } else {
-                cut4(xa, himask, a1, a2, a3);
-                cut4(xb, himask, b1, b2, b3);
+                cut4(xa.x, xa.y, xa.z, xa.w, himask, a1, a2, a3);
+                cut4(xb.x, xb.y, xb.z, xb.w, himask, b1, b2, b3);
             }
             const uint32_t d = wr + e * 8 * ROWB;
             *LDS_AS(u32x2, (uintptr_t)d) = a1;
@@ -459,7 +435,7 @@ __device__ __forceinline__ void tns_block(const SQ& sq, const int bid, unsigned 
 #pragma unroll
             for (int j = 0; j < NCT; ++j)
 #pragma unroll
-                for (int i = 0; i < NTM; ++i) acc[i][j] = mfma16(af[i][ai], bf[bi][j], acc[i][j]);
+                for (int i = 0; i < NTM; ++i) acc[i][j] = mfma_bf16_16(af[i][ai], bf[bi][j], acc[i][j]);
         }
     };
 

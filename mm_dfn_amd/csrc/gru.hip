@@ -192,13 +192,6 @@ struct BwdGroups {
     int32_t* kout[MAXG];           // (rows): steps run per truncated row (with dhinit)
 };
 
-// Gate non-linearities on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1 ulp each): the
-// accurate libm expf/tanhf are ~600 cycles of dependent scalar code per timestep on the serial critical
-// path of the recurrence (tools/ubench/step_latency.hip).  Absolute error < 3e-7, far inside the 1e-5 parity
-// budget of the encoders (logits 1e-4).
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // A use of a freshly loaded register BEFORE the time loop.  Without it the compiler sinks loop-invariant global loads to
@@ -1745,24 +1738,14 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
                                  const float* const* b_hh, float* const* y, float* const* gates, const int* rows,
                                  const int* T, int H, void* riders, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
+    const GruForm f = mmdfn_gru_form(ngroups, rows);
+    const int R = f.R;
     FwdGroups G;
-    G.n = ngroups;
-    G.abl = 0;
+    if (!mmdfn_gru_fill_fwd(G, ngroups, gi, w_hh, b_hh, y, gates, rows, T, R)) return -1;
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_ABL")) G.abl = atoi(e);
 #endif
-    const GruForm f = mmdfn_gru_form(ngroups, rows);
-    const int R = f.R;
-    int sl = 0;
-    for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0 || T[g] <= 0) return -1;
-        G.gi[g] = gi[g]; G.y[g] = y[g]; G.gates[g] = gates[g];
-        G.w_hh[2 * g] = w_hh[2 * g]; G.w_hh[2 * g + 1] = w_hh[2 * g + 1];
-        G.b_hh[2 * g] = b_hh[2 * g]; G.b_hh[2 * g + 1] = b_hh[2 * g + 1];
-        G.rows[g] = rows[g]; G.T[g] = T[g]; G.slice0[g] = sl;
-        sl += (rows[g] + R - 1) / R;
-    }
-    G.slice0[ngroups] = sl;
+    const int sl = G.slice0[ngroups];
     dim3 grid(sl, 2), block(NT);
     hipStream_t s = (hipStream_t)stream;
     MmdfnRiders* rd = (MmdfnRiders*)riders;
@@ -1806,19 +1789,11 @@ extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const floa
                                  const float* const* gates, const float* const* w_hh, float* const* dgi,
                                  float* const* dgh, const int* rows, const int* T, int H, void* riders, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
-    BwdGroups G;
-    G.n = ngroups;
     const GruForm f = mmdfn_gru_form(ngroups, rows);
     const int R = f.R;
-    int sl = 0;
-    for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0 || T[g] <= 0) return -1;
-        G.dy[g] = dy[g]; G.y[g] = y[g]; G.gates[g] = gates[g]; G.dgi[g] = dgi[g];
-        G.w_hh[2 * g] = w_hh[2 * g]; G.w_hh[2 * g + 1] = w_hh[2 * g + 1];
-        G.dgh[g] = dgh[g]; G.rows[g] = rows[g]; G.T[g] = T[g]; G.slice0[g] = sl;
-        sl += (rows[g] + R - 1) / R;
-    }
-    G.slice0[ngroups] = sl;
+    BwdGroups G;
+    if (!mmdfn_gru_fill_bwd(G, ngroups, dy, y, gates, w_hh, dgi, dgh, rows, T, R)) return -1;
+    const int sl = G.slice0[ngroups];
     dim3 grid(sl, 2), block(NT);
     hipStream_t s = (hipStream_t)stream;
     MmdfnRiders* rd = (MmdfnRiders*)riders;
@@ -1829,7 +1804,8 @@ extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const floa
         if (f.idle_cus > 0 && rd != nullptr && rd->rider.valid && rd->rider.tq.n <= MMDFN_RIDER_MAXSEG) {
             // a staged weight-gradient batch rides on the CUs this launch leaves idle (gru_seq_bwd_riders_kernel)
             const TnSplitSegs& rp = rd->rider.tq;
-            const TnRiderSegs rq = mmdfn_rider_table(rp);
+            TnRiderSegs rq;
+            mmdfn_seg_copy(rq, rp);
             const int ngru8 = (2 * sl + 7) & ~7;
             if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel)) return e;
             hipLaunchKernelGGL(gru_seq_bwd_riders_kernel, dim3(ngru8 + rp.wg_prefix[rp.n]), dim3(512), tnsb::LDS_B, s, G, rq, sl, ngru8);
@@ -1869,14 +1845,8 @@ extern "C" int mmdfn_gru_seq_fwd_seg(int ngroups, const float* const* gi, const 
                                      const int* tdir, const float* const* ytab, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
     FwdGroups G;
-    G.n = ngroups;
-    G.abl = 0;
+    if (!mmdfn_gru_fill_fwd(G, ngroups, gi, w_hh, b_hh, y, gates, rows, T, 0)) return -1;
     for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0 || T[g] <= 0) return -1;
-        G.gi[g] = gi[g]; G.y[g] = y[g]; G.gates[g] = gates[g];
-        G.w_hh[2 * g] = w_hh[2 * g]; G.w_hh[2 * g + 1] = w_hh[2 * g + 1];
-        G.b_hh[2 * g] = b_hh[2 * g]; G.b_hh[2 * g + 1] = b_hh[2 * g + 1];
-        G.rows[g] = rows[g]; G.T[g] = T[g]; G.slice0[g] = 0;
         G.ytab[g] = ytab ? ytab[g] : nullptr;
         if (G.ytab[g] != nullptr && (rank == nullptr || rank[g] == nullptr || tdir[g] != 1)) return -1;   // a start table serves the reverse direction
     }
@@ -1908,12 +1878,8 @@ extern "C" int mmdfn_gru_seq_bwd_seg(int ngroups, const float* const* dy, const 
                                      float* const* dhinit, int32_t* const* kout, void* stream) {
     if (ngroups <= 0 || ngroups > MAXG || H != GH) return -1;
     BwdGroups G;
-    G.n = ngroups;
+    if (!mmdfn_gru_fill_bwd(G, ngroups, dy, y, gates, w_hh, dgi, dgh, rows, T, 0)) return -1;
     for (int g = 0; g < ngroups; ++g) {
-        if (rows[g] <= 0 || T[g] <= 0) return -1;
-        G.dy[g] = dy[g]; G.y[g] = y[g]; G.gates[g] = gates[g]; G.dgi[g] = dgi[g];
-        G.w_hh[2 * g] = w_hh[2 * g]; G.w_hh[2 * g + 1] = w_hh[2 * g + 1];
-        G.dgh[g] = dgh[g]; G.rows[g] = rows[g]; G.T[g] = T[g]; G.slice0[g] = 0;
         G.dhinit[g] = dhinit ? dhinit[g] : nullptr;
         G.kout[g] = kout ? kout[g] : nullptr;
         if ((G.dhinit[g] != nullptr) != (G.kout[g] != nullptr)) return -1;

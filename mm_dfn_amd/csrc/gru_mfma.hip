@@ -5,9 +5,8 @@
 // GRUs) like gru.hip, whose kernels give every sequence-direction a workgroup of its own: there the step is a dependent
 // chain of packed FMAs on the weights held in registers, ~0.65-1.2 us per step whatever the batch, and a launch lasts as long
 // as ceil(sequences / 512) rounds of T steps.  At cfg3 that is 3-4 rounds.  Here a workgroup owns 16 rows of one (group,
-// direction):   gh^T (300 x 16) = W_hh (300 x 100) . h_{t-1}^T (100 x 16)   per step as v_mfma_f32_16x16x32_bf16 with every
-// fp32 operand cut exactly into three bf16 pieces and the six piece products of weight >= 2^-16 (fp32-level error, see
-// propagate_split.hip): the launch lasts T steps of ~2.4 us for up to 16 x 256 sequences.
+// direction):   gh^T (300 x 16) = W_hh (300 x 100) . h_{t-1}^T (100 x 16)   per step as v_mfma_f32_16x16x32_bf16 on the six
+// piece products of bf16_pieces.h (fp32-level error): the launch lasts T steps of ~2.4 us for up to 16 x 256 sequences.
 //   forward : wave w (7 waves) owns hidden units 16 w .. 16 w + 15: its three gate tiles (r, z, n) x 4 K-steps of W_hh pieces
 //             stay in registers (144 VGPRs) as the MFMA's A operand (rows = units); the B operand (k x 16 sequences) is
 //             h_{t-1} as three bf16 planes [sequence][unit] in LDS, written by the lanes that produce h_t: a lane's D fragment
@@ -29,10 +28,6 @@
 namespace {
 
 constexpr int GH = 100;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#define LDS_AS(T, p) ((__attribute__((address_space(3))) T*)(p))
 
 constexpr int MS = 16;                  // sequences per workgroup
 constexpr int NWV = 7;                  // waves: 7 x 16 = 112 >= 100 hidden units
@@ -43,41 +38,10 @@ constexpr int HPLANE = MS * HROWB;      // 4 352
 constexpr int DROWB = 656;              // bytes per sequence row of a dgh plane: 320 bf16 + 16 (164 dwords = 4 x 9 mod 64)
 constexpr int DPLANE = MS * DROWB;      // 10 496
 
-__device__ __forceinline__ float as_f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-// four values -> their three bf16 pieces (8 + 8 + 8 significant bits, cut by truncation, each exactly representable)
-__device__ __forceinline__ void cut4(float x0, float x1, float x2, float x3, u32x2& p1, u32x2& p2, u32x2& p3) {
-    const uint32_t hm = 0xffff0000u;
-    p1 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-    x0 -= as_f(as_u(x0) & hm); x1 -= as_f(as_u(x1) & hm); x2 -= as_f(as_u(x2) & hm); x3 -= as_f(as_u(x3) & hm);
-    p2 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-    x0 -= as_f(as_u(x0) & hm); x1 -= as_f(as_u(x1) & hm); x2 -= as_f(as_u(x2) & hm); x3 -= as_f(as_u(x3) & hm);
-    p3 = u32x2{__builtin_amdgcn_perm(as_u(x1), as_u(x0), 0x07060302u), __builtin_amdgcn_perm(as_u(x3), as_u(x2), 0x07060302u)};
-}
-
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 // The per-step barrier: the planes written this step must be complete (lgkmcnt), the step's GLOBAL stores need not be --
 // __syncthreads() also waits for vmcnt(0), i.e. for a store round trip per step (0.6 us of the first version's 2.5 us step).
 __device__ __forceinline__ void step_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// the six piece products of one K = 32 step, smallest first
-__device__ __forceinline__ f32x4 six(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4 c) {
-    c = mfma16(a[2], b[0], c);
-    c = mfma16(a[1], b[0], c);
-    c = mfma16(a[1], b[1], c);
-    c = mfma16(a[0], b[2], c);
-    c = mfma16(a[0], b[1], c);
-    c = mfma16(a[0], b[0], c);
-    return c;
 }
 
 constexpr int MAXG = 8;
@@ -102,16 +66,6 @@ struct MfBwd {
     int rows[MAXG], T[MAXG], slice0[MAXG + 1];
     int abl;
 };
-
-// eight consecutive k of one weight row -> the three pieces of an A fragment register set
-__device__ __forceinline__ void cut8(const float (&v)[8], u32x4& p1, u32x4& p2, u32x4& p3) {
-    u32x2 a1, a2, a3, b1, b2, b3;
-    cut4(v[0], v[1], v[2], v[3], a1, a2, a3);
-    cut4(v[4], v[5], v[6], v[7], b1, b2, b3);
-    p1 = u32x4{a1.x, a1.y, b1.x, b1.y};
-    p2 = u32x4{a2.x, a2.y, b2.x, b2.y};
-    p3 = u32x4{a3.x, a3.y, b3.x, b3.y};
-}
 
 // LDS staging of the steps' operands (filled by the I/O waves): one slot per step parity
 constexpr int GROW = 3 * GH;                    // forward: gi of one sequence (r | z | n), 300 floats = 44 (mod 64) dwords apart
@@ -217,7 +171,7 @@ __device__ __forceinline__ void gru_fwd_mfma_body(const MfFwd& G, const int bx, 
                     const int k = 32 * ks + 8 * g4 + e;
                     v[e] = (ua < GH && k < GH) ? w_hh[(int64_t)(gate * GH + ua) * GH + k] : 0.f;
                 }
-                cut8(v, wf[gate][ks][0], wf[gate][ks][1], wf[gate][ks][2]);
+                cut8(v, BF16_HI, wf[gate][ks][0], wf[gate][ks][1], wf[gate][ks][2]);
             }
     }
     float bhr[4], bhz[4], bhn[4];
@@ -275,7 +229,7 @@ __device__ __forceinline__ void gru_fwd_mfma_body(const MfFwd& G, const int bx, 
         }
         if (uok) {
             u32x2 p1, p2, p3;
-            cut4(hn[0], hn[1], hn[2], hn[3], p1, p2, p3);
+            cut4(hn[0], hn[1], hn[2], hn[3], BF16_HI, p1, p2, p3);
             const uint32_t wb = wr + (cur ^ 1) * 3 * HPLANE;
             *LDS_AS(u32x2, (uintptr_t)wb) = p1;
             *LDS_AS(u32x2, (uintptr_t)(wb + HPLANE)) = p2;
@@ -407,7 +361,7 @@ __device__ __forceinline__ void gru_bwd_mfma_body(const MfBwd& G, const int bx, 
                 const int j = 32 * ks + 8 * g4 + e;
                 v[e] = (ua < GH && j < 3 * GH) ? w_hh[(int64_t)j * GH + ua] : 0.f;
             }
-            cut8(v, wf[ks][0], wf[ks][1], wf[ks][2]);
+            cut8(v, BF16_HI, wf[ks][0], wf[ks][1], wf[ks][2]);
         }
     }
     const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) void*)dp);
@@ -461,15 +415,15 @@ __device__ __forceinline__ void gru_bwd_mfma_body(const MfBwd& G, const int bx, 
         if (uok) {
             const uint32_t wb = wr + cur * 3 * DPLANE;
             u32x2 p1, p2, p3;
-            cut4(drp[0], drp[1], drp[2], drp[3], p1, p2, p3);
+            cut4(drp[0], drp[1], drp[2], drp[3], BF16_HI, p1, p2, p3);
             *LDS_AS(u32x2, (uintptr_t)wb) = p1;
             *LDS_AS(u32x2, (uintptr_t)(wb + DPLANE)) = p2;
             *LDS_AS(u32x2, (uintptr_t)(wb + 2 * DPLANE)) = p3;
-            cut4(dzp[0], dzp[1], dzp[2], dzp[3], p1, p2, p3);
+            cut4(dzp[0], dzp[1], dzp[2], dzp[3], BF16_HI, p1, p2, p3);
             *LDS_AS(u32x2, (uintptr_t)(wb + 2 * GH)) = p1;
             *LDS_AS(u32x2, (uintptr_t)(wb + 2 * GH + DPLANE)) = p2;
             *LDS_AS(u32x2, (uintptr_t)(wb + 2 * GH + 2 * DPLANE)) = p3;
-            cut4(dgn[0], dgn[1], dgn[2], dgn[3], p1, p2, p3);
+            cut4(dgn[0], dgn[1], dgn[2], dgn[3], BF16_HI, p1, p2, p3);
             *LDS_AS(u32x2, (uintptr_t)(wb + 4 * GH)) = p1;
             *LDS_AS(u32x2, (uintptr_t)(wb + 4 * GH + DPLANE)) = p2;
             *LDS_AS(u32x2, (uintptr_t)(wb + 4 * GH + 2 * DPLANE)) = p3;
@@ -515,19 +469,8 @@ int mmdfn_launch_gru_fwd_mfma(const GruForm& f, int ngroups, const float* const*
                               MmdfnRiders* riders, hipStream_t s) {
     if (ngroups <= 0 || ngroups > MAXG) return -2;
     MfFwd G;
-    G.n = ngroups;
-    int sl = 0;
-    for (int g = 0; g < MAXG; ++g) {
-        const bool on = g < ngroups;
-        G.gi[g] = on ? gi[g] : nullptr; G.y[g] = on ? y[g] : nullptr; G.gates[g] = on ? gates[g] : nullptr;
-        G.w_hh[2 * g] = on ? w_hh[2 * g] : nullptr; G.w_hh[2 * g + 1] = on ? w_hh[2 * g + 1] : nullptr;
-        G.b_hh[2 * g] = on ? b_hh[2 * g] : nullptr; G.b_hh[2 * g + 1] = on ? b_hh[2 * g + 1] : nullptr;
-        G.rows[g] = on ? rows[g] : 0; G.T[g] = on ? T[g] : 0; G.slice0[g] = sl;
-        if (on) sl += (rows[g] + MS - 1) / MS;
-    }
-    G.slice0[MAXG] = sl;
-    for (int g = ngroups; g < MAXG; ++g) G.slice0[g] = sl;
-    G.abl = 0;
+    if (!mmdfn_gru_fill_fwd(G, ngroups, gi, w_hh, b_hh, y, gates, rows, T, MS)) return -1;
+    const int sl = G.slice0[ngroups];
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_MF_ABL")) G.abl = atoi(e);
 #endif
@@ -553,23 +496,13 @@ int mmdfn_launch_gru_bwd_mfma(const GruForm& f, int ngroups, const float* const*
                               const int* rows, const int* T, MmdfnRiders* riders, hipStream_t s) {
     if (ngroups <= 0 || ngroups > MAXG) return -2;
     MfBwd G;
-    G.n = ngroups;
-    int sl = 0;
-    for (int g = 0; g < MAXG; ++g) {
-        const bool on = g < ngroups;
-        G.dy[g] = on ? dy[g] : nullptr; G.y[g] = on ? y[g] : nullptr; G.gates[g] = on ? gates[g] : nullptr;
-        G.w_hh[2 * g] = on ? w_hh[2 * g] : nullptr; G.w_hh[2 * g + 1] = on ? w_hh[2 * g + 1] : nullptr;
-        G.dgi[g] = on ? dgi[g] : nullptr; G.dgh[g] = on ? dgh[g] : nullptr;
-        G.rows[g] = on ? rows[g] : 0; G.T[g] = on ? T[g] : 0; G.slice0[g] = sl;
-        if (on) sl += (rows[g] + MS - 1) / MS;
-    }
-    G.slice0[MAXG] = sl;
-    for (int g = ngroups; g < MAXG; ++g) G.slice0[g] = sl;
-    G.abl = 0;
+    if (!mmdfn_gru_fill_bwd(G, ngroups, dy, y, gates, w_hh, dgi, dgh, rows, T, MS)) return -1;
+    const int sl = G.slice0[ngroups];
     if (f.idle_cus > 0 && riders != nullptr && riders->rider.valid && riders->rider.tq.n <= MMDFN_RIDER_MAXSEG) {
         // a staged weight-gradient batch rides on the CUs this launch leaves idle
         const TnSplitSegs& rp = riders->rider.tq;
-        const TnRiderSegs rq = mmdfn_rider_table(rp);
+        TnRiderSegs rq;
+        mmdfn_seg_copy(rq, rp);
         const int ngru8 = (2 * sl + 7) & ~7;
         if (int e = mmdfn_allow_big_lds(gru_seq_bwd_mfma_riders_kernel)) return e;
         hipLaunchKernelGGL(gru_seq_bwd_mfma_riders_kernel, dim3(ngru8 + rp.wg_prefix[rp.n]), dim3(BWD_THREADS), BWD_LDS, s, G, rq, sl,

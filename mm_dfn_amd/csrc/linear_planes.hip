@@ -16,7 +16,7 @@
 //     no cutting, no LDS, no barrier on the B side;
 //   * A (the X rows) is cut once per workgroup -- 1/4 per wave -- into LDS in A-fragment order (16 bytes per lane, conflict
 //     free), two k-steps (32 k) per phase, double-buffered, one barrier per phase.
-// Arithmetic: the six piece products of weight >= 2^-16 of propagate_split.hip (fp32-level error; exact pieces by truncation).
+// Arithmetic: the six piece products of bf16_pieces.h.
 // Plane layout: planes_common.h; the main loop: planes_pipeline.h (shared with the GCN stack's plane kernels, gcn_planes.hip).
 #include "planes_common.h"
 #include "../../include/mmdfn_hip.h"
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void cut_planes_kernel(CutTable T) {
         for (int j = 0; j < 8; ++j) x[j] = cut_element(T, i, n, k0 + j);      // (transposed modes: lanes walk a stored row)
     }
     u32x4 p1, p2, p3;
-    pl_cut8(x, p1, p2, p3);
+    cut8_pairs(x, BF16_HI, p1, p2, p3);
     u32x4* dst = T.planes[i] + (int64_t)f * 3 * 64 + lane;
     dst[0] = p1;
     dst[64] = p2;
@@ -213,7 +213,7 @@ __device__ __forceinline__ void linear_planes_body(
             }                                                                                               \
         }                                                                                                   \
         u32x4 p1_, p2_, p3_;                                                                                \
-        pl_cut8(x_, p1_, p2_, p3_);                                                                         \
+        cut8_pairs(x_, BF16_HI, p1_, p2_, p3_);                                                             \
         u32x4* dst_ = &As[(BUF) * (PL_LDS / 2) + ((sksl * 3) * 2 + shf) * 64 + lane];                       \
         dst_[0] = p1_;                                                                                      \
         dst_[2 * 64] = p2_;                                                                                 \

@@ -3,36 +3,21 @@
 //
 // Replaces nn.Linear / F.linear on the hot path (the hoisted GRU input contractions model.py:866,868, the GCN input
 // layer and LSTM gate pre-activations model_GCN.py:454,466) where the row count is large enough to fill the chip
-// with 128 x 128 output tiles.  Same arithmetic as propagate_split.hip: every fp32 operand is cut exactly into three
-// bf16 pieces and the six piece products of weight >= 2^-16 are issued as v_mfma_f32_32x32x16_bf16 (fp32-level
-// error, 2.7x less matrix-pipe time than exact-f32 MFMAs).  X (R, K) and W (N, K) are both k-contiguous, so
+// with 128 x 128 output tiles.  Same arithmetic as propagate_split.hip: the six piece products of bf16_pieces.h as
+// v_mfma_f32_32x32x16_bf16 (2.7x less matrix-pipe time than exact-f32 MFMAs).  X (R, K) and W (N, K) are both k-contiguous, so
 //   A = X rows go HBM/L2 -> registers in MFMA layout (four 16-byte loads per lane per 32-wide k chunk),
 //   B = W rows (one per output column) are cut once per workgroup (two 16-byte loads per staging task) and parked in
 //       LDS as three bf16 [col][k-slot] arrays whose 16-byte reads are the B fragments,
 // and the chunk loop is the shared software pipeline of split_mfma_pipeline.h.  The epilogue adds the bias, applies
 // ReLU / the accumulate addend and stores straight from the accumulators (a 32x32 tile row is 128 contiguous bytes).
-#include "mmdfn_internal.h"
+#include "bf16_pieces.h"
 #include "../../include/mmdfn_hip.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int SBK = 32;
 constexpr int SROW = 20;
-
-__device__ __forceinline__ float as_f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_bf16_16(u32x4 a, u32x4 b, f32x4 c) {     // (the pipeline's tail tile)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // One 128 x 128 output block:  Yb[r][c] = act( sum_k Xb[r][k] Wb[c][k] + bias[c] ) (+ Yb[r][c])  for r < Rv, c < Nstore;
 // columns Nv <= c < Nstore are written as exact zeros (row padding of the block-tile layout).

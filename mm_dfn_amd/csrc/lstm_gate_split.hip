@@ -3,10 +3,9 @@
 // (reference model_GCN.py:463-467: nn.LSTM with seq_len 1) with the contraction on the bf16 matrix path.
 //
 // gcn_stack.hip's lstm_gate_fwd_ws_kernel runs the same stage on exact-f32 MFMAs (16 x 16 x 4: 1/16 of the bf16 rate) and
-// measures 61 us = 64 TFLOP/s at 24 576 rows, its matrix pipe ~35 % busy.  Here every fp32 operand is cut exactly into three
-// bf16 pieces and the six piece products of weight >= 2^-16 are issued as v_mfma_f32_32x32x16_bf16 -- the arithmetic and the
-// software pipeline of propagate_split.hip / linear_split.hip (split_mfma_pipeline.h: fp32-level error, 2.7x less
-// matrix-pipe time).  What is specific to this kernel:
+// measures 61 us = 64 TFLOP/s at 24 576 rows, its matrix pipe ~35 % busy.  Here the contraction runs on the six piece products of
+// bf16_pieces.h as v_mfma_f32_32x32x16_bf16, in the software pipeline of propagate_split.hip / linear_split.hip
+// (split_mfma_pipeline.h: 2.7x less matrix-pipe time).  What is specific to this kernel:
 //   * workgroup = 128 rows x (4 gates x 32 units): accumulator column tile ct IS gate ct, so a lane ends up with the four
 //     pre-activations of its (row, unit) pairs in its own registers and the cell math runs straight from the
 //     accumulators -- no staging of G through LDS or memory;
@@ -14,31 +13,13 @@
 //     (H % 4 == 0), so each load picks its source with one select;
 //   * gate activations (read again only by the backward pass) leave through nontemporal stores.
 // Unit blocks are the fast grid index: the four blocks of a row tile run back to back and share its q / h rows through L2.
-#include "mmdfn_internal.h"
+#include "bf16_pieces.h"
 #include "../../include/mmdfn_hip.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int SBK = 32;
 constexpr int SROW = 20;
-
-__device__ __forceinline__ float as_f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_bf16_16(u32x4 a, u32x4 b, f32x4 c) {     // (the pipeline's tail tile)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// the gate non-linearities of gcn_stack.hip (hardware exp / rcp forms, |err| < 3e-7)
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // Piece planes of [W_ih | W_hh] for the BPRE form (the cell is shared by all layers of the stack and constant inside a step,
 // model_GCN.py:466: cut ONCE per step by lstm_gate_cut_kernel instead of by every workgroup of every layer's launch).  Layout =
@@ -64,6 +45,8 @@ __global__ __launch_bounds__(256) void lstm_gate_cut_kernel(const float* __restr
         const int64_t row = (int64_t)(gate * H + unit) * H;
         v[j] = (unit < H && k < 2 * H) ? (k < H ? Wih[row + k] : Whh[row + k - H]) : 0.f;
     }
+    // (the cut of bf16_pieces.h, all eight values stage by stage: a third statement order, kept because both cut8 forms move
+    // this kernel's schedule)
     uint32_t pc[3][4];
     float x[8];
 #pragma unroll
@@ -73,7 +56,7 @@ __global__ __launch_bounds__(256) void lstm_gate_cut_kernel(const float* __restr
 #pragma unroll
         for (int p2 = 0; p2 < 4; ++p2) pc[q][p2] = __builtin_amdgcn_perm(as_u(x[2 * p2 + 1]), as_u(x[2 * p2]), 0x07060302u);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] -= as_f(as_u(x[j]) & 0xffff0000u);
+        for (int j = 0; j < 8; ++j) x[j] -= as_f(as_u(x[j]) & BF16_HI);
     }
     u32x4* dst = planes + ((int64_t)(ub * nchunks + cc) * 3 * 4 + slot) * GPL_SLOT + bcol;
 #pragma unroll
@@ -185,7 +168,7 @@ constexpr bool SPLIT_TAIL = false;     // (four full 32-column tiles)
     for (int r = 0; r < 16; ++r) {
         const int row = r0 + wrow0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
         if (row >= R) continue;
-        const float gi = sigm(acc[0][r] + bi), gf = sigm(acc[1][r] + bf), gg = tanhf_(acc[2][r] + bg), go = sigm(acc[3][r] + bo);
+        const float gi = sigmoidf_(acc[0][r] + bi), gf = sigmoidf_(acc[1][r] + bf), gg = tanhf_(acc[2][r] + bg), go = sigmoidf_(acc[3][r] + bo);
         const float cn = gf * cp[r] + gi * gg;
         const float hn = go * tanhf_(cn);
         float* gr = gates + (int64_t)row * 4 * H + unit;

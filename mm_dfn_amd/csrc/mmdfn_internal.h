@@ -63,6 +63,18 @@ __device__ __forceinline__ float half_sum32(float v) {
     return (threadIdx.x & 32) ? hi : lo;
 }
 
+// Gate non-linearities on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1 ulp each): the accurate libm expf /
+// tanhf are ~600 cycles of dependent scalar code per timestep on the serial critical path of the GRU recurrence
+// (tools/ubench/step_latency.hip), and the LSTM cell of the GCN stack evaluates six per element -- more issue slots than the
+// contraction next to it.  Absolute error < 3e-7, far inside the 1e-5 parity budget of the encoders and the stack (logits 1e-4).
+__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+// the libm form, for the pointwise kernels off the critical path (gcn_pointwise.hip, fusion.hip)
+__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
 // more than 64 KB of dynamic LDS per workgroup needs the attribute raised once per kernel (gfx950: 160 KB per CU)
 template <class Kern>
 inline int mmdfn_allow_big_lds(Kern kern) {
@@ -133,19 +145,34 @@ int mmdfn_launch_tile_dot(const float* X, const float* Y, float* out_tiles, floa
 #define MMDFN_TNS_BK 32
 #define MMDFN_TNS_TM 128
 #define MMDFN_TNS_TN 112
-constexpr int MMDFN_TNS_MAXSEG = 40;
-struct TnSplitSegs {
-    const float* A[MMDFN_TNS_MAXSEG];
-    const float* B[MMDFN_TNS_MAXSEG];
-    float* part[MMDFN_TNS_MAXSEG];
-    float* colpart[MMDFN_TNS_MAXSEG];
-    int R[MMDFN_TNS_MAXSEG], lda[MMDFN_TNS_MAXSEG], ldb[MMDFN_TNS_MAXSEG], bshift[MMDFN_TNS_MAXSEG];
-    int rows_per_split[MMDFN_TNS_MAXSEG], splits[MMDFN_TNS_MAXSEG], tiles[MMDFN_TNS_MAXSEG], nblocks[MMDFN_TNS_MAXSEG];
-    int M[MMDFN_TNS_MAXSEG], N[MMDFN_TNS_MAXSEG];
-    int wide[MMDFN_TNS_MAXSEG];          // != 0: 128 x (2 MMDFN_TNS_TN) tiles, nblocks counts 224-column blocks (gemm_tn_split.hip)
-    int wg_prefix[MMDFN_TNS_MAXSEG + 1];
+template <int CAP>
+struct TnSegTable {
+    const float* A[CAP];
+    const float* B[CAP];
+    float* part[CAP];
+    float* colpart[CAP];
+    int R[CAP], lda[CAP], ldb[CAP], bshift[CAP];
+    int rows_per_split[CAP], splits[CAP], tiles[CAP], nblocks[CAP];
+    int M[CAP], N[CAP];
+    int wide[CAP];          // != 0: 128 x (2 MMDFN_TNS_TN) tiles, nblocks counts 224-column blocks (gemm_tn_split.hip)
+    int wg_prefix[CAP + 1];
     int n;
 };
+// the first min(CD, CS) slots of s (and its n) as a table of another capacity; the rest of d is zero
+template <int CD, int CS>
+inline void mmdfn_seg_copy(TnSegTable<CD>& d, const TnSegTable<CS>& s) {
+    constexpr int m = CD < CS ? CD : CS;
+    auto cp = [](auto& dst, const auto& src, int cnt) { for (int k = 0; k < cnt; ++k) dst[k] = src[k]; };
+    d = TnSegTable<CD>();
+    cp(d.A, s.A, m); cp(d.B, s.B, m); cp(d.part, s.part, m); cp(d.colpart, s.colpart, m);
+    cp(d.R, s.R, m); cp(d.lda, s.lda, m); cp(d.ldb, s.ldb, m); cp(d.bshift, s.bshift, m);
+    cp(d.rows_per_split, s.rows_per_split, m); cp(d.splits, s.splits, m); cp(d.tiles, s.tiles, m); cp(d.nblocks, s.nblocks, m);
+    cp(d.M, s.M, m); cp(d.N, s.N, m); cp(d.wide, s.wide, m); cp(d.wg_prefix, s.wg_prefix, m + 1);
+    d.n = s.n;
+}
+// (the two capacities are named types, not aliases: the kernels that take them by value keep their symbols)
+constexpr int MMDFN_TNS_MAXSEG = 40;
+struct TnSplitSegs : TnSegTable<MMDFN_TNS_MAXSEG> {};
 int mmdfn_launch_gemm_tn_split(const TnSplitSegs& sq, hipStream_t s);
 
 // Riders of the GRU recurrence launches (gru.hip, gru_mfma.hip): work STAGED in a caller-owned MmdfnRiders context instead of
@@ -154,31 +181,8 @@ int mmdfn_launch_gemm_tn_split(const TnSplitSegs& sq, hipStream_t s);
 // recurrence leaves idle; mmdfn_riders_launched then files the batch's slab reduction.  What a launch did not take is launched
 // the ordinary way by mmdfn_wgrad_riders_flush / mmdfn_keep_flags_flush.
 constexpr int MMDFN_RIDER_MAXSEG = 16;
-struct TnRiderSegs {
-    const float* A[MMDFN_RIDER_MAXSEG];
-    const float* B[MMDFN_RIDER_MAXSEG];
-    float* part[MMDFN_RIDER_MAXSEG];
-    float* colpart[MMDFN_RIDER_MAXSEG];
-    int R[MMDFN_RIDER_MAXSEG], lda[MMDFN_RIDER_MAXSEG], ldb[MMDFN_RIDER_MAXSEG], bshift[MMDFN_RIDER_MAXSEG];
-    int rows_per_split[MMDFN_RIDER_MAXSEG], splits[MMDFN_RIDER_MAXSEG], tiles[MMDFN_RIDER_MAXSEG], nblocks[MMDFN_RIDER_MAXSEG];
-    int M[MMDFN_RIDER_MAXSEG], N[MMDFN_RIDER_MAXSEG];
-    int wide[MMDFN_RIDER_MAXSEG];
-    int wg_prefix[MMDFN_RIDER_MAXSEG + 1];
-    int n;
-};
-inline TnRiderSegs mmdfn_rider_table(const TnSplitSegs& t) {      // (t.n <= MMDFN_RIDER_MAXSEG)
-    TnRiderSegs rq;
-    for (int k = 0; k < MMDFN_RIDER_MAXSEG; ++k) {
-        rq.A[k] = t.A[k]; rq.B[k] = t.B[k]; rq.part[k] = t.part[k]; rq.colpart[k] = t.colpart[k];
-        rq.R[k] = t.R[k]; rq.lda[k] = t.lda[k]; rq.ldb[k] = t.ldb[k]; rq.bshift[k] = t.bshift[k];
-        rq.rows_per_split[k] = t.rows_per_split[k]; rq.splits[k] = t.splits[k]; rq.tiles[k] = t.tiles[k];
-        rq.nblocks[k] = t.nblocks[k]; rq.M[k] = t.M[k]; rq.N[k] = t.N[k]; rq.wide[k] = t.wide[k];
-        rq.wg_prefix[k] = t.wg_prefix[k];
-    }
-    rq.wg_prefix[MMDFN_RIDER_MAXSEG] = t.wg_prefix[t.n];
-    rq.n = t.n;
-    return rq;
-}
+struct TnRiderSegs : TnSegTable<MMDFN_RIDER_MAXSEG> {};      // what a recurrence launch carries (mmdfn_seg_copy of a batch's table)
+static_assert(sizeof(TnSplitSegs) == 3208 && sizeof(TnRiderSegs) == 1288, "kernel-argument layouts of the segment tables");
 
 constexpr int TN_MAXOUT = 40;      // outputs of one weight-gradient batch's reduction launch (gemm_tn.hip)
 namespace kfb {
@@ -211,6 +215,7 @@ struct MmdfnRiders {
     kfb::FlagJob flag_job;
     bool flag_job_valid;
 };
+static_assert(sizeof(MmdfnRiders) == 8400, "mmdfn_riders_bytes(): what callers allocate");
 int mmdfn_riders_launched(MmdfnRiders* riders, hipStream_t s);
 
 // How the plain (unsegmented) recurrence launch of these groups runs: the MFMA form (16 sequences per workgroup) or R sequences
@@ -230,3 +235,44 @@ int mmdfn_launch_gru_fwd_mfma(const GruForm& f, int ngroups, const float* const*
 int mmdfn_launch_gru_bwd_mfma(const GruForm& f, int ngroups, const float* const* dy, const float* const* y,
                               const float* const* gates, const float* const* w_hh, float* const* dgi, float* const* dgh,
                               const int* rows, const int* T, MmdfnRiders* riders, hipStream_t s);
+
+// Host fillers of the recurrence launches' group tables (gru.hip FwdGroups / BwdGroups, gru_mfma.hip MfFwd / MfBwd: kernel
+// arguments passed by value, the same leading fields in both files).  A filler value-initialises the table, copies the ngroups
+// live slots and lays the groups' workgroup slices end to end, per_wg sequences per workgroup: slice0[g] = first slice of group
+// g, slice0[ngroups ..] = their total (per_wg = 0: a segmented launch, whose workgroups are chains -- every slice0 stays 0).
+// false = a group without rows or steps.  What only one table has (abl, seg, ytab, dhinit, kout) is set by the caller.
+template <class Tab>
+inline bool mmdfn_gru_fill(Tab& G, int ngroups, const float* const* w_hh, const int* rows, const int* T, int per_wg) {
+    constexpr int maxg = sizeof(G.rows) / sizeof(G.rows[0]);
+    G = Tab();
+    G.n = ngroups;
+    int sl = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        if (rows[g] <= 0 || T[g] <= 0) return false;
+        G.w_hh[2 * g] = w_hh[2 * g]; G.w_hh[2 * g + 1] = w_hh[2 * g + 1];
+        G.rows[g] = rows[g]; G.T[g] = T[g]; G.slice0[g] = sl;
+        if (per_wg > 0) sl += (rows[g] + per_wg - 1) / per_wg;
+    }
+    for (int g = ngroups; g <= maxg; ++g) G.slice0[g] = sl;
+    return true;
+}
+template <class Tab>
+inline bool mmdfn_gru_fill_fwd(Tab& G, int ngroups, const float* const* gi, const float* const* w_hh, const float* const* b_hh,
+                               float* const* y, float* const* gates, const int* rows, const int* T, int per_wg) {
+    if (!mmdfn_gru_fill(G, ngroups, w_hh, rows, T, per_wg)) return false;
+    for (int g = 0; g < ngroups; ++g) {
+        G.gi[g] = gi[g]; G.y[g] = y[g]; G.gates[g] = gates[g];
+        G.b_hh[2 * g] = b_hh[2 * g]; G.b_hh[2 * g + 1] = b_hh[2 * g + 1];
+    }
+    return true;
+}
+template <class Tab>
+inline bool mmdfn_gru_fill_bwd(Tab& G, int ngroups, const float* const* dy, const float* const* y, const float* const* gates,
+                               const float* const* w_hh, float* const* dgi, float* const* dgh, const int* rows, const int* T,
+                               int per_wg) {
+    if (!mmdfn_gru_fill(G, ngroups, w_hh, rows, T, per_wg)) return false;
+    for (int g = 0; g < ngroups; ++g) {
+        G.dy[g] = dy[g]; G.y[g] = y[g]; G.gates[g] = gates[g]; G.dgi[g] = dgi[g]; G.dgh[g] = dgh[g];
+    }
+    return true;
+}

@@ -48,9 +48,9 @@
             _Pragma("unroll") for (int q_ = 0; q_ < 3; ++q_) {                                              \
                 const int ahi_ = 2 - q_, alo_ = (q_ == 0) ? 1 : 0, blo_ = (q_ < 2) ? 1 : 2;                 \
                 _Pragma("unroll") for (int h_ = 0; h_ < RH; ++h_)                                           \
-                    acc[h_][0] = pl_mfma(a_[j_][h_][ahi_], bq[PAR][j_][0], acc[h_][0]);                     \
+                    acc[h_][0] = mfma_bf16(a_[j_][h_][ahi_], bq[PAR][j_][0], acc[h_][0]);                   \
                 _Pragma("unroll") for (int h_ = 0; h_ < RH; ++h_)                                           \
-                    acc[h_][NACC - 1] = pl_mfma(a_[j_][h_][alo_], bq[PAR][j_][blo_], acc[h_][NACC - 1]);    \
+                    acc[h_][NACC - 1] = mfma_bf16(a_[j_][h_][alo_], bq[PAR][j_][blo_], acc[h_][NACC - 1]);  \
             }                                                                                               \
         }                                                                                                   \
         if ((PH) + 1 < NPH) {                                                                               \

@@ -1,14 +1,11 @@
 // K6 (large-dialogue variant): out = A_hat . H with the fp32 product carried by bf16 MFMAs.
 //
 // Replaces torch.spmm(adj, input) (reference model_GCN.py:178) like propagate.hip, for launches that are
-// bound by the exact-f32 MFMA rate (v_mfma_f32_16x16x4_f32: 32 cycles per 2 kflop on a SIMD).  Each fp32
-// operand is cut -- exactly, by truncation -- into three bf16 pieces  x = x1 + x2 + x3  (8 + 8 + 8
-// significant bits) and the product is assembled from the six piece products whose weight is >= 2^-16:
-//     a.b ~= a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1          (dropped: a2b3 + a3b2 + a3b3 <= 2^-23 |a||b|)
-// Every piece product is exact in the fp32 accumulator, so the result carries fp32-level error (the dropped
-// terms are the size of one fp32 rounding of a.b; measured max |err| vs an fp64 product: 1.8e-7, the same as
-// the f32-MFMA kernel) while six bf16 MFMAs per K=16 replace four f32 MFMAs per K=16 at 1/16 of the cycles
-// per flop: 2.7x less matrix-pipe time.
+// bound by the exact-f32 MFMA rate (v_mfma_f32_16x16x4_f32: 32 cycles per 2 kflop on a SIMD).  The product
+// is assembled from three exact bf16 pieces per operand and their six piece products (bf16_pieces.h): the
+// dropped terms are the size of one fp32 rounding of a.b (measured max |err| vs an fp64 product: 1.8e-7, the
+// same as the f32-MFMA kernel) while six bf16 MFMAs per K=16 replace four f32 MFMAs per K=16 at 1/16 of the
+// cycles per flop: 2.7x less matrix-pipe time.
 //
 // Work decomposition: workgroup = (dialogue, modality, 128 tile rows, 128 feature columns); 4 waves x 32 rows x
 // 4 v_mfma_f32_32x32x16_bf16 column tiles.
@@ -26,27 +23,13 @@
 //     what bounds it.)
 // Cross-modal diagonals are added in the LDS row epilogue as in propagate.hip.  XCD mapping: blockIdx % 8 ==
 // dialogue % 8.
-#include "mmdfn_internal.h"
+#include "bf16_pieces.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int SBK = 32;    // k per chunk = two K=16 MFMA steps
 constexpr int SROW = 20;   // LDS row stride in dwords: 16 (32 bf16) + 4 pad; 16 consecutive rows -> 64 banks
-
-__device__ __forceinline__ float as_f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t as_u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_bf16_16(u32x4 a, u32x4 b, f32x4 c) {     // (the pipeline's tail tile)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // ABLC (profiling aid, compile time): 1 = no cutting stages, 2 = no MFMAs, 4 = no MFMAs of the fourth column tile (the
 // upper bound of what a tail tile for columns 96.. can buy at d = 100; results wrong)

@@ -1,9 +1,9 @@
 // Shared main loop of the bf16-piece MFMA kernels (propagate_split.hip, linear_split.hip): a CODE FRAGMENT included
 // inside the kernel body, not a header of declarations.
 //
-// Computes, for one workgroup (4 waves x 32 rows x 4 column tiles of 32),  acc[ct] += A (128 x K) . B (K x 128)  with
-// every fp32 operand cut exactly into three bf16 pieces and the six piece products of weight >= 2^-16 issued as
-// v_mfma_f32_32x32x16_bf16 (see propagate_split.hip for the arithmetic).  K is walked in chunks of 32.
+// Computes, for one workgroup (4 waves x 32 rows x 4 column tiles of 32),  acc[ct] += A (128 x K) . B (K x 128)  on
+// the six piece products of bf16_pieces.h as v_mfma_f32_32x32x16_bf16 (the cut itself is staged here, one stage behind
+// each MFMA, instead of calling that header's helpers).  K is walked in chunks of 32.
 //
 // k permutation inside a chunk: MFMA step kh (0,1), lane group kg (0,1), element e (0..7)  <->
 //      k = 16 kh + 8 (e >> 2) + 4 kg + (e & 3)

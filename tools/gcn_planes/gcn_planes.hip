@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 4) void gcnii_layer_fwd_planes_kernel(
         float x_[8] = {ok0_ ? raw[PAR][0].x : 0.f, ok0_ ? raw[PAR][0].y : 0.f, ok0_ ? raw[PAR][0].z : 0.f, ok0_ ? raw[PAR][0].w : 0.f, \
                        ok1_ ? raw[PAR][1].x : 0.f, ok1_ ? raw[PAR][1].y : 0.f, ok1_ ? raw[PAR][1].z : 0.f, ok1_ ? raw[PAR][1].w : 0.f}; \
         u32x4 p1_, p2_, p3_;                                                                                \
-        pl_cut8(x_, p1_, p2_, p3_);                                                                         \
+        cut8_pairs(x_, BF16_HI, p1_, p2_, p3_);                                                             \
         u32x4* dst_ = &As[(BUF) * (PL_LDS / 2) + ((sksl * 3) * 2 + shf) * 64 + lane];                       \
         dst_[0] = p1_;                                                                                      \
         dst_[2 * 64] = p2_;                                                                                 \
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, 4) void gcnii_layer_bwd_planes_kernel(
             if (ok1_) *reinterpret_cast<f32x4*>(dprow + k0_ + 4) = pb_;                                     \
         }                                                                                                   \
         u32x4 p1_, p2_, p3_;                                                                                \
-        pl_cut8(x_, p1_, p2_, p3_);                                                                         \
+        cut8_pairs(x_, BF16_HI, p1_, p2_, p3_);                                                             \
         u32x4* dst_ = &As[(BUF) * (PL_LDS / 2) + ((sksl * 3) * 2 + shf) * 64 + lane];                       \
         dst_[0] = p1_;                                                                                      \
         dst_[2 * 64] = p2_;                                                                                 \
@@ -296,8 +296,8 @@ __global__ __launch_bounds__(256, 3) void lstm_gate_bwd_planes_kernel(
                 if (has_h) dc_prev[irow[i_] * H + u_] = dc_ * gf_;                                          \
             }                                                                                               \
             uint32_t a1_, a2_, a3_, b1_, b2_, b3_;                                                          \
-            pl_cut2(di_, df_, a1_, a2_, a3_);                                                               \
-            pl_cut2(dg_, dO_, b1_, b2_, b3_);                                                               \
+            cut2(di_, df_, BF16_HI, a1_, a2_, a3_);                                                         \
+            cut2(dg_, dO_, BF16_HI, b1_, b2_, b3_);                                                             \
             /* k = 4 u + g inside the phase: k-step uloc >> 2, k group (uloc & 3) >> 1, 8-byte half uloc & 1 */ \
             const int rl_ = (tid >> 3) + 32 * i_;                                                           \
             const int slot_ = (rl_ & 31) + 32 * ((uloc & 3) >> 1);                                          \
