@@ -46,7 +46,8 @@ extern "C" {
  * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
 int64_t mmdfn_riders_bytes(void);
 
-/* Library / device sanity: returns the ABI version (currently 21: 20 + the TFN tensor-fusion kernels mmdfn_tfn_{workspace,fwd,bwd_input,bwd_weight,keep_flags};
+/* Library / device sanity: returns the ABI version (currently 22: 21 + FlatAdam on device-resident step state mmdfn_adam_state_bytes, mmdfn_grad_sumsq,
+ * mmdfn_adam_prepare, mmdfn_adam_step_state; 21 = 20 + the TFN tensor-fusion kernels mmdfn_tfn_{workspace,fwd,bwd_input,bwd_weight,keep_flags};
  * 20 = 19 + mmdfn_linear_planes_group_in (input dropout in the
  * plane projection's staging step), mmdfn_linear_planes_group_party (party-ordered store) and mmdfn_linear_group_seg2 (two K segments per few-row problem); 19 = 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
  * and the LMF fusion kernels mmdfn_lmf_{fwd,bwd,bwd_width}; 18 = 17 with the rider hand-off made explicit -- the rider context
@@ -579,6 +580,41 @@ int mmdfn_wgrad_riders_drain(void* riders, void* stream, int discard);
  * ------------------------------------------------------------------------- */
 int mmdfn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step, void* stream);
+
+/* ABI 22: the same update on DEVICE-RESIDENT step state (csrc/optimizer_state.hip).  mmdfn_adam_step takes the step count from the
+ * host, so a captured launch of it would repeat step 1 for ever; here the count, the bias corrections, lr / weight decay, the
+ * global gradient norm, its clipping factor and the skip decision live in a caller-owned block of DEVICE memory
+ * (mmdfn_adam_state_bytes() = 64 bytes, 16-byte aligned) and no launch takes an argument that changes from step to step: the
+ * three launches below can be nodes of a captured training step.  The host writes step / enabled / skip_nonfinite / lr /
+ * weight_decay / max_norm (ordinary stream-ordered copies); the kernels write the rest. */
+typedef struct mmdfn_adam_state {
+  int32_t step;            /* steps applied so far */
+  int32_t enabled;         /* 0: every kernel below leaves p, m, v and step untouched */
+  int32_t skip_nonfinite;
+  int32_t skipped;         /* running count of skipped steps */
+  int32_t last_skipped;    /* 1 if the latest call was skipped */
+  float lr, weight_decay, max_norm;     /* max_norm <= 0: no clipping */
+  float grad_norm, scale;               /* outputs of the latest call */
+  float bc1, bc2_sqrt;
+  int32_t reserved[4];
+} mmdfn_adam_state;
+/* Every entry point below returns -1 and launches nothing on n <= 0, a null pointer, or a state block / float buffer (g, p, m,
+ * v: read as 16-byte vectors) that is not 16-byte aligned. */
+int64_t mmdfn_adam_state_bytes(void);
+/* sum of g[i]^2 over n floats (16-byte aligned), accumulated in double: one partial per workgroup in partials[0 .. *nparts)
+ * (*nparts = min(ceil(n / 4 / 256), 1024, nparts_cap) >= 1, written to HOST memory by the call itself); lanes, waves and
+ * workgroups are reduced in a fixed order and without atomics, so the same data gives the same bits. */
+int mmdfn_grad_sumsq(const float* g, int64_t n, double* partials, int nparts_cap, int* nparts, void* stream);
+/* One workgroup, in front of mmdfn_adam_step_state.  With st->enabled == 0 it writes nothing.  Otherwise: the partials summed
+ * in index order (partials == NULL: the norm is not wanted -- grad_norm = 0, scale = 1, never skipped; else 1 <= nparts <= 1024);
+ * grad_norm = (float)sqrt(sum); scale = max_norm > 0 ? min(1, max_norm / (grad_norm + 1e-6f)) : 1 (torch's clip_grad_norm_);
+ * last_skipped = skip_nonfinite && !isfinite(sum).  A skipped step counts in `skipped`; any other does ++step and leaves the
+ * new step's bias corrections bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step) (computed in double, rounded once). */
+int mmdfn_adam_prepare(mmdfn_adam_state* st, const double* partials, int nparts, float beta1, float beta2, void* stream);
+/* mmdfn_adam_step's arithmetic with lr, weight_decay, bc1 and bc2_sqrt read from *st and g replaced by scale * g when scale < 1;
+ * returns at once when !enabled || last_skipped (p, m, v untouched: non-finite gradients never reach them).  The same grid. */
+int mmdfn_adam_step_state(float* p, const float* g, float* m, float* v, int64_t n, const mmdfn_adam_state* st, float beta1,
+                          float beta2, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K9  classifier head (reference model.py:1328-1337: dropout_ -> ReLU -> smax_fc -> log_softmax) as one launch each way:

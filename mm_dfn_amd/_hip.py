@@ -102,6 +102,10 @@ SIGNATURES = {
     "mmdfn_focal_loss_fwd_ignore": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _L, _P],
     "mmdfn_focal_loss_bwd_ignore": [_P, _P, _P, _P, _P, _L, _I, _L, _P],
     "mmdfn_adam_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
+    "mmdfn_adam_state_bytes": [],
+    "mmdfn_grad_sumsq": [_P, _L, _P, _I, _P, _P],
+    "mmdfn_adam_prepare": [_P, _P, _I, _F, _F, _P],
+    "mmdfn_adam_step_state": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _P],
     "mmdfn_party_gather": [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "mmdfn_party_gather_bwd": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "mmdfn_party_gather_bwd_colsum": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
@@ -117,7 +121,20 @@ SIGNATURES = {
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
+
+
+class AdamState(ctypes.Structure):
+    """Mirror of ``mmdfn_adam_state`` (include/mmdfn_hip.h): FlatAdam's step state, 64 bytes of device memory."""
+    _fields_ = [("step", ctypes.c_int32), ("enabled", ctypes.c_int32), ("skip_nonfinite", ctypes.c_int32),
+                ("skipped", ctypes.c_int32), ("last_skipped", ctypes.c_int32),
+                ("lr", _F), ("weight_decay", _F), ("max_norm", _F), ("grad_norm", _F), ("scale", _F),
+                ("bc1", _F), ("bc2_sqrt", _F), ("reserved", ctypes.c_int32 * 4)]
+
+
+def adam_state_word(name):
+    """Index of field ``name`` in the block viewed as 16 four-byte words."""
+    return getattr(AdamState, name).offset // 4
 
 
 class HipLibraryError(RuntimeError):

@@ -4,7 +4,9 @@ At IEMOCAP sizes a step is a few hundred short kernels; launched eagerly the hos
 dispatch) is the bottleneck, not the GPU.  For a fixed batch signature (same dialogue lengths) the step is
 static, so it is captured once into a hipGraph and replayed: one launch per step.  Gradients are written
 into persistent tensors (views of the data-parallel flat bucket when one is given), so an eager RCCL
-all-reduce / optimizer step can follow each replay.
+all-reduce / optimizer step can follow each replay -- or, with a device-state ``FlatAdam`` (``optimizer=``), the gradient
+pack and the update are the last nodes of the graph itself and nothing follows a replay on the host but the bookkeeping
+of the weight piece planes.
 """
 import torch
 
@@ -13,21 +15,44 @@ from .layout import recording
 
 
 class CapturedStep:
-    def __init__(self, model, step_fn, warmup=3, bucket=None, reduce_in_graph=False):
+    def __init__(self, model, step_fn, warmup=3, bucket=None, reduce_in_graph=False, optimizer=None):
         """step_fn() must run forward + backward on STATIC input tensors and return the loss tensor.
         The step is captured with every ``.grad`` set to None, so autograd simply hands its gradient
         buffers over (no zero-fill, no accumulate kernels); with a ``bucket`` the captured graph ends with
         the single multi-tensor pack into the flat all-reduce buffer and, with ``reduce_in_graph``, the RCCL
-        all-reduce of that buffer as a graph node (no host launch between backward and the collective)."""
+        all-reduce of that buffer as a graph node (no host launch between backward and the collective).
+        ``optimizer``: a FlatAdam on device-resident step state (``capturable=True``, ``max_grad_norm``, ``skip_nonfinite``); the
+        captured pass then ends with the pack into ITS bucket and its update launches, and every replay is a whole training
+        step.  The warm-up passes lay out the optimizer's flat buffers (``prepare_for_capture``) and never launch the update.
+        Single process only: not with ``reduce_in_graph``."""
+        if optimizer is not None:
+            if reduce_in_graph:
+                raise ValueError("CapturedStep: optimizer= with reduce_in_graph=True (a multi-rank in-graph step) is not supported")
+            if not getattr(optimizer, "device_state", False):
+                raise ValueError("CapturedStep: optimizer= needs a FlatAdam on device-resident step state (capturable=True, "
+                                 "max_grad_norm or skip_nonfinite): a host step count would be baked into the graph")
+            if bucket is not None and bucket is not optimizer.bucket:
+                raise ValueError("CapturedStep: optimizer= brings its own bucket (optimizer.bucket)")
+            bucket = optimizer.bucket
         self.model = model
         self.bucket = bucket
+        self.optimizer = optimizer
         # the graph bakes the addresses of every tensor step_fn closes over (static inputs, index tensors, labels):
         # holding the closure keeps them allocated for the lifetime of the graph
         self._step_fn = step_fn
 
-        def tail():
+        def tail(update=False):
             ops.join_weight_grads()          # flush weight gradients still queued (normally the engine callback did)
-            if bucket is not None:
+            if optimizer is not None:
+                if update:
+                    bucket.flatten(attach=False)
+                    optimizer.step(grads_already_flat=True)
+                else:
+                    # warm-up: pack, lay out the flat parameter / moment buffers and the state block; no update
+                    if bucket.flat is not None:
+                        bucket.flatten(attach=False)
+                    optimizer.prepare_for_capture()
+            elif bucket is not None:
                 bucket.flatten()
                 if reduce_in_graph:
                     bucket.reduce_flat()
@@ -42,7 +67,10 @@ class CapturedStep:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
+            laid_out = optimizer is not None and optimizer.flat_p is None
+            # (a first warm-up pass that re-pointed the parameters into the optimizer's flat buffer is followed by one more: the
+            # weight piece planes are then cut from the new storages before the capture, not inside it)
+            for _ in range(max(warmup, 1) + (1 if laid_out else 0)):
                 model.zero_grad(set_to_none=True)
                 step_fn()
                 tail()
@@ -60,7 +88,7 @@ class CapturedStep:
             # thread_local: a communication-library watchdog thread polling its own events must not invalidate the capture
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                 self.loss = step_fn()
-                tail()
+                tail(update=True)
         self._pinned = list(used)
         self._planes = list(planes)
         self._rng_per_replay = ops.flags_consumed(dev_index) - consumed0      # Philox counters one replay consumes
@@ -81,6 +109,7 @@ class CapturedStep:
         self._pinned = []
         self._planes = []
         self._step_fn = None
+        self.optimizer = None
         if graph is not None:
             torch.cuda.synchronize()
             graph.reset()
@@ -96,7 +125,15 @@ class CapturedStep:
             ops.flag_state_sync(self._dev_index)           # torch.manual_seed / a restored RNG state since the last draw
         if self._planes:
             ops.refresh_planes(self._planes)               # (host-side version check; a launch only after a weight update)
+        if self.optimizer is not None:
+            self.optimizer._push_hyper()                   # lr / weight decay changed since the last launch (a scheduler)
         self.graph.replay()
+        if self.optimizer is not None:
+            # the graph's last node wrote the parameters: every piece plane is stale.  The cut stays OUTSIDE the graph (the
+            # refresh above, in front of the next launch, as after an eager optimizer step): which planes are fresh is host
+            # bookkeeping shared by everything that reads them -- eager forward passes, eval entries, the other entries of a
+            # cache -- and the next reader need not be this graph
+            ops.invalidate_planes()
         if self._rng_per_replay:
             ops.flags_advance_host(self._dev_index, self._rng_per_replay)
         return self.loss

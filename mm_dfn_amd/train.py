@@ -72,12 +72,14 @@ class StepGraphCache:
     at cfg2).  The reference re-seeds before every pass (run_train_erc.py:164), so the shuffle -- and with it the
     set of batch signatures -- is the same every epoch: after the first epoch every step of a real run is a replay.
     Each entry owns static input buffers (a batch is copied in, ~5 MB), the captured forward(+loss+backward) and its
-    outputs; gradients are handed to ``p.grad`` after the replay, the optimizer step stays outside the graph.  Least
-    recently used entries are dropped beyond ``max_entries`` (each holds a private memory pool)."""
+    outputs; gradients are handed to ``p.grad`` after the replay, the optimizer step stays outside the graph -- unless the
+    cache is given the ``optimizer`` (a FlatAdam on device-resident step state): training entries then end with the gradient
+    pack and the update, and a replay is the whole step.  Least recently used entries are dropped beyond ``max_entries``
+    (each holds a private memory pool)."""
 
     IGNORE = -100                  # label of the padding dialogue's utterances (bucketed entries)
 
-    def __init__(self, model, loss_f, max_entries=96, warmup=2, bucket_rows=0, larger_bucket_fallback=True):
+    def __init__(self, model, loss_f, max_entries=96, warmup=2, bucket_rows=0, larger_bucket_fallback=True, optimizer=None):
         """``bucket_rows`` = g > 0: BUCKETED entries -- one captured step per (train / eval, B, padded length L, ceil((N + 1) /
         g) g) instead of per exact tuple of dialogue lengths (N = the batch's utterances).  The batch is padded to its
         bucket with ONE extra dialogue of 1..g utterances (fixed random features, labels IGNORE: dialogues never interact
@@ -92,8 +94,16 @@ class StepGraphCache:
         instead of being captured in the middle of a pass (55-90 ms at cfg2 against a few percent more rows for that step);
         ``fallbacks`` counts them, ``precapture`` still captures every bucket it meets exactly.
         Needs a mm_dfn_amd FocalLoss (its ignore_index form) and a model without use_speaker / use_modal (they slice by
-        dialogue length on the host); anything else falls back to exact signatures."""
+        dialogue length on the host); anything else falls back to exact signatures.
+        ``optimizer``: a device-state FlatAdam (``capturable=True`` / ``max_grad_norm`` / ``skip_nonfinite``) captured into every
+        TRAINING entry, exact and bucketed (graphs.CapturedStep(optimizer=...)); eval entries are captured without it.  The pass
+        loop must then not step it again (train_or_eval_graph_model does not), and ``precapture`` replays with the update
+        disabled."""
         from collections import OrderedDict
+        if optimizer is not None and not getattr(optimizer, "device_state", False):
+            raise ValueError("StepGraphCache: optimizer= needs a FlatAdam on device-resident step state (capturable=True, "
+                             "max_grad_norm or skip_nonfinite)")
+        self.optimizer = optimizer
         self.model, self.loss_f = model, loss_f
         self.max_entries, self.warmup = max_entries, warmup
         self.bucket_rows = int(bucket_rows or 0)
@@ -146,17 +156,22 @@ class StepGraphCache:
         item 7: a pass that has to capture pays ~25 ms per new entry in the middle of its steps).  Walks the loader once --
         the loader's length histogram is what decides the set, so this is the loader the passes will use or one drawn like
         it -- and steps only the first batch of each new key (forward + loss + backward into the entry's own gradient
-        buffers; no optimizer, no metrics; dropout draws are put back by CapturedStep).  Returns the number of entries
+        buffers; no optimizer -- a cache-owned one is disabled on the device for the walk, so the replays update nothing --, no
+        metrics; dropout draws are put back by CapturedStep).  Returns the number of entries
         captured; the model's ``.grad`` fields are left as they were.  Call it AFTER anything that re-points parameter storage
         (FlatAdam lays the parameters out at its first step; ``.to()``; ``load_state_dict(assign=True)``): a captured step bakes
         the storages and is captured again when they move."""
         grads = [(p, p.grad) for p in self.model.parameters()]
         made = 0
         self._exact_buckets = True
+        if self.optimizer is not None:
+            self.optimizer.set_enabled(False)
         try:
             made = self._precapture_walk(loader, train_flag, device)
         finally:
             self._exact_buckets = False
+            if self.optimizer is not None:
+                self.optimizer.set_enabled(True)
         if hasattr(loader, "bind_graph_cache"):
             self.forget_queued()
         for p, g in grads:
@@ -257,7 +272,7 @@ class StepGraphCache:
             mode = model.training
             model.train(train_flag)
             with torch.set_grad_enabled(bool(train_flag)):
-                cap = CapturedStep(model, fn, warmup=self.warmup)
+                cap = CapturedStep(model, fn, warmup=self.warmup, optimizer=self.optimizer if train_flag else None)
             model.train(mode)
             ent = dict(static=static, cap=cap, out=out, flat=flat, pos=pos, pending=None, scope=scope, set_padding=set_padding,
                        state=state, bucketed=True, B=B)
@@ -369,7 +384,7 @@ class StepGraphCache:
             mode = model.training
             model.train(train_flag)
             with torch.set_grad_enabled(bool(train_flag)):
-                cap = CapturedStep(model, fn, warmup=self.warmup)
+                cap = CapturedStep(model, fn, warmup=self.warmup, optimizer=self.optimizer if train_flag else None)
             model.train(mode)
             # everything the graph reads that was allocated OUTSIDE the capture must live as long as the graph: the
             # static inputs, the label gather index and the flattened labels (the closure itself is kept by cap)
@@ -416,9 +431,20 @@ class StepGraphCache:
 def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=False, optimizer=None, cuda_flag=False,
                               modals=None, target_names=None, test_label=False, tensorboard=False, seed=2021,
                               step_hook=None, graph_cache=None):
-    """``graph_cache``: a StepGraphCache (or None = launch every step eagerly, as before)."""
+    """``graph_cache``: a StepGraphCache (or None = launch every step eagerly, as before).  A cache that owns its optimizer
+    (StepGraphCache(optimizer=...)) steps it inside the replayed graph: ``optimizer`` must be that object, there is no place
+    for a ``step_hook`` between backward and update, and only steps that bypass the cache (``test_label``) call
+    ``optimizer.step()`` here."""
     losses, preds, labels = [], [], []
     assert not train_flag or optimizer is not None
+    in_graph_opt = graph_cache is not None and getattr(graph_cache, "optimizer", None) is not None
+    if in_graph_opt and train_flag:
+        if optimizer is not graph_cache.optimizer:
+            raise ValueError("train_or_eval_graph_model: graph_cache steps its own optimizer inside the captured step; pass that "
+                             "object as optimizer")
+        if step_hook is not None:
+            raise ValueError("train_or_eval_graph_model: step_hook cannot run between backward and an optimizer step that are "
+                             "nodes of one captured graph (StepGraphCache(optimizer=...))")
     model.train() if train_flag else model.eval()
     seed_everything(seed)
     vids = []
@@ -431,7 +457,9 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
             optimizer.zero_grad()         # (a replayed step hands over fresh gradient tensors: nothing to reset)
         textf, visuf, acouf, qmask, umask, label = [d.cuda() for d in data[:6]] if cuda_flag else data[:6]
         lengths = getattr(data, "lengths", None) or lengths_from_umask(umask)
+        stepped_in_graph = False
         if graph_cache is not None and not test_label:      # (the --test_label dumps call .cpu() / np.save: never captured)
+            stepped_in_graph = in_graph_opt and train_flag
             loss, log_prob, flat = graph_cache.step((textf, visuf, acouf, qmask, umask, label), lengths, train_flag,
                                                     test_label)
             # metrics are deferred to the end of the pass: the step's predictions, labels and loss stay where the graph
@@ -457,9 +485,10 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
                 backward(loss)
         if train_flag:
             ops.join_weight_grads()       # weight gradients still queued are written to .grad here
-            if step_hook is not None:
-                step_hook(model)          # e.g. data-parallel gradient all-reduce
-            optimizer.step()
+            if not stepped_in_graph:      # (else the replayed graph ended with the pack and the update)
+                if step_hook is not None:
+                    step_hook(model)          # e.g. data-parallel gradient all-reduce
+                optimizer.step()
         if len(data) > 6:
             vids = data[6]
     if not preds:
