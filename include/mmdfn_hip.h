@@ -46,7 +46,8 @@ extern "C" {
  * staged, a GRU launch takes nothing, a weight-gradient batch merges nothing. */
 int64_t mmdfn_riders_bytes(void);
 
-/* Library / device sanity: returns the ABI version (currently 22: 21 + FlatAdam on device-resident step state mmdfn_adam_state_bytes, mmdfn_grad_sumsq,
+/* Library / device sanity: returns the ABI version (currently 23: 22 + the graph kind of the adjacency build mmdfn_adj_build_kind,
+ * mmdfn_adj_build_bwd_kind; 22 = 21 + FlatAdam on device-resident step state mmdfn_adam_state_bytes, mmdfn_grad_sumsq,
  * mmdfn_adam_prepare, mmdfn_adam_step_state; 21 = 20 + the TFN tensor-fusion kernels mmdfn_tfn_{workspace,fwd,bwd_input,bwd_weight,keep_flags};
  * 20 = 19 + mmdfn_linear_planes_group_in (input dropout in the
  * plane projection's staging step), mmdfn_linear_planes_group_party (party-ordered store) and mmdfn_linear_group_seg2 (two K segments per few-row problem); 19 = 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
@@ -112,6 +113,33 @@ int mmdfn_adj_build_bwd(const float* dtiles, const float* dcross,
                         float* dfeats, const float* addend,
                         const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
                         int B, int M, int N, int D, int max_len, float modal_weight, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K5 with the graph kind as an argument (ABI 23).  Same operands, layouts and scratch as mmdfn_adj_build /
+ * mmdfn_adj_build_bwd; forward and backward of one tensor set take the same kind.
+ *   kind 0 : the angular-similarity graph above -- mmdfn_adj_build / _bwd are these calls with kind 0.
+ *   kind 1 : the arccos-distance graph of the MMGCN baseline (MM_GCN2.create_big_adj, model_mm.py:241-296) and of
+ *            GCNII_lyc without an adjacency (message_passing_wo_speaker, model_GCN.py:490-511, the M = 1 case):
+ *              within a modality   A[(m,p),(m,q)] = acos(0.99999 cos(x_mp, x_mq))   (radians, diagonal included:
+ *                                  cos(x, x) is taken as the constant 1 there, cosg holds 1, no gradient flows through it)
+ *              between modalities  A[(m,r),(n,r)] = c, a constant: the `modal_weight` slot carries c
+ *              (MM_GCN2 passes 0.99999); degree = row sum, A_hat = D^-1/2 A D^-1/2 as for kind 0.
+ *            cdot is written as zeros (no cross cosine is formed).  Backward: the constant entries reach the
+ *            features through the degrees only, so dcross contributes to d(degree) and ecross is written as zeros.
+ *   any other kind returns -1.
+ * ------------------------------------------------------------------------- */
+int mmdfn_adj_build_kind(const float* feats, float* unit, float* norm, float* cosg, float* cdot,
+                         float* rdeg, float* tiles, float* cross,
+                         const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
+                         int B, int M, int N, int D, int max_len, float modal_weight, int kind, void* stream);
+
+int mmdfn_adj_build_bwd_kind(const float* dtiles, const float* dcross,
+                             const float* unit, const float* norm, const float* cosg, const float* cdot,
+                             const float* rdeg, const float* tiles, const float* cross,
+                             float* wsym, float* etile, float* ecross, float* ddeg, float* dunit,
+                             float* dfeats, const float* addend,
+                             const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
+                             int B, int M, int N, int D, int max_len, float modal_weight, int kind, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K2  fused GRU recurrence (replaces the time loop inside nn.GRU for ``lstm_l``

@@ -22,6 +22,8 @@ SIGNATURES = {
     "mmdfn_tile_outer": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "mmdfn_adj_build": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
     "mmdfn_adj_build_bwd": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
+    "mmdfn_adj_build_kind": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
+    "mmdfn_adj_build_bwd_kind": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
     "mmdfn_riders_bytes": [],
     "mmdfn_gru_seq_fwd": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "mmdfn_gru_seq_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
@@ -121,7 +123,7 @@ SIGNATURES = {
     "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
 }
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class AdamState(ctypes.Structure):

@@ -54,6 +54,13 @@ __device__ __forceinline__ float ks_dsim(float c) {
     const float ac = c * MMDFN_COS_SHRINK;
     return (MMDFN_COS_SHRINK / MMDFN_PI_F) * __builtin_amdgcn_rsqf(1.0f - ac * ac);
 }
+// the same for the arccos kind: d acos(a c) / d c = -a / sqrt((1 - a c)(1 + a c))  (mmdfn_dsim_k<1>)
+template <int KIND>
+__device__ __forceinline__ float ks_dsim_k(float c) {
+    if (KIND == 0) return ks_dsim(c);
+    const float ac = c * MMDFN_COS_SHRINK;
+    return -MMDFN_COS_SHRINK * __builtin_amdgcn_rsqf((1.0f - ac) * (1.0f + ac));
+}
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 
 // blockIdx -> (dialogue, modality, strip): blockIdx % 8 == dialogue % 8 (everything of a dialogue shares one XCD's L2)
@@ -70,7 +77,8 @@ __device__ __forceinline__ bool ks_decode(int B, int M, int NS, int& i, int& m, 
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // forward, stage A.  LDS: U[lmax_p][SU] | part[8][SR] | seed[SR] | rr[SR]
-template <int SR>
+// (KIND: mmdfn_internal.h.  KIND 1 reads no other modality's rows: its cross-modal entries are the constant modal_weight carries)
+template <int SR, int KIND>
 __global__ __launch_bounds__(64 * KS_NW) void adj_strip_fwd_kernel(
     const float* __restrict__ feats, float* __restrict__ unit, float* __restrict__ norm, float* __restrict__ cosg,
     float* __restrict__ cdot, float* __restrict__ rdeg, float* __restrict__ tiles, float* __restrict__ cross,
@@ -139,8 +147,8 @@ __global__ __launch_bounds__(64 * KS_NW) void adj_strip_fwd_kernel(
 #pragma unroll
                 for (int j = 0; j < RI; ++j) {
                     if (r0 + 32 * j >= Lp) continue;
-                    if (o0 >= 0) xo[j][0][sidx] = *reinterpret_cast<const float4*>(f0 + offo[j] + 64 * sidx);
-                    if (o1 >= 0) xo[j][1][sidx] = *reinterpret_cast<const float4*>(f1 + offo[j] + 64 * sidx);
+                    if (KIND == 0 && o0 >= 0) xo[j][0][sidx] = *reinterpret_cast<const float4*>(f0 + offo[j] + 64 * sidx);
+                    if (KIND == 0 && o1 >= 0) xo[j][1][sidx] = *reinterpret_cast<const float4*>(f1 + offo[j] + 64 * sidx);
                 }
             }
         }
@@ -189,21 +197,23 @@ __global__ __launch_bounds__(64 * KS_NW) void adj_strip_fwd_kernel(
         for (int oi = 0; oi < 2; ++oi) {
             const int o = oi == 0 ? o0 : o1;
             if (o < 0) continue;
-            float ss = 0.f;
-#pragma unroll
-            for (int sidx = 0; sidx < 4; ++sidx) ss += dot4(xo[j][oi][sidx], xo[j][oi][sidx]);
-            ss = sum16(ss);
-            const float nv = sqrtf(ss);
-            const float inv = 1.0f / nv;
             float sdot = 0.f;
+            if (KIND == 0) {
+                float ss = 0.f;
 #pragma unroll
-            for (int sidx = 0; sidx < 4; ++sidx) {
-                float4 u = xo[j][oi][sidx];
-                u.x = div_by(u.x, nv, inv); u.y = div_by(u.y, nv, inv); u.z = div_by(u.z, nv, inv); u.w = div_by(u.w, nv, inv);
-                sdot += dot4(um[sidx], u);
+                for (int sidx = 0; sidx < 4; ++sidx) ss += dot4(xo[j][oi][sidx], xo[j][oi][sidx]);
+                ss = sum16(ss);
+                const float nv = sqrtf(ss);
+                const float inv = 1.0f / nv;
+#pragma unroll
+                for (int sidx = 0; sidx < 4; ++sidx) {
+                    float4 u = xo[j][oi][sidx];
+                    u.x = div_by(u.x, nv, inv); u.y = div_by(u.y, nv, inv); u.z = div_by(u.z, nv, inv); u.w = div_by(u.w, nv, inv);
+                    sdot += dot4(um[sidx], u);
+                }
+                sdot = sum16(sdot);
             }
-            sdot = sum16(sdot);
-            const float c = mmdfn_sim(sdot) * modal_weight;
+            const float c = KIND == 0 ? mmdfn_sim(sdot) * modal_weight : modal_weight;
             dsum += c;
             if (m < o && fi == 0 && rok) {               // every pair has one writer: the workgroup of its lower modality
                 const int64_t oo = (int64_t)mmdfn_pair_index(m, o, M) * N + rs + p;
@@ -257,8 +267,9 @@ __global__ __launch_bounds__(64 * KS_NW) void adj_strip_fwd_kernel(
                 const int pl = 16 * a + 4 * g + r;
                 const int p = r0 + pl;
                 const bool in = (p < L) && (q < L);
-                if (p < L && q < ld) cosg[toff + (int64_t)p * ld + q] = in ? acc[a][r] : 0.f;     // raw cosine (saved for backward)
-                sv[a][r] = in ? mmdfn_sim(acc[a][r]) : 0.f;
+                const float gv = (KIND == 1 && p == q) ? 1.0f : acc[a][r];     // (kind 1: cos(x, x) = 1, mmdfn_internal.h)
+                if (p < L && q < ld) cosg[toff + (int64_t)p * ld + q] = in ? gv : 0.f;     // raw cosine (saved for backward)
+                sv[a][r] = in ? mmdfn_sim_k<KIND>(gv) : 0.f;
                 const float rsum = sum16(sv[a][r]);
                 if (fi == 0) part[b * SR + pl] = rsum;
             }
@@ -337,7 +348,7 @@ __global__ __launch_bounds__(256) void adj_finish_kernel(float* __restrict__ til
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // backward.  LDS: Rw[SR][KS_SE] | Ct[SR][KS_SE] | colp[3][16][128] | zrow[3][128] | dd[3][128] | rl[3][128] | ec[3][SR] | dUl[SR][SD]
-template <int SR>
+template <int SR, int KIND>
 __global__ __launch_bounds__(64 * KS_NW) void adj_strip_bwd_kernel(
     const float* __restrict__ dtiles, const float* __restrict__ dcross, const float* __restrict__ unit,
     const float* __restrict__ norm, const float* __restrict__ cosg, const float* __restrict__ cdot,
@@ -569,13 +580,15 @@ __global__ __launch_bounds__(64 * KS_NW) void adj_strip_bwd_kernel(
                 const int q = lane + 64 * e;
                 if (q >= L) continue;
                 const float wv = Rw[pl * KS_SE + q] + Ct[pl * KS_SE + q];
-                Rw[pl * KS_SE + q] = (wv * rp * rm[q] + ddp + dm[q]) * ks_dsim(cg[j][e]);
+                const float ev = (wv * rp * rm[q] + ddp + dm[q]) * ks_dsim_k<KIND>(cg[j][e]);
+                Rw[pl * KS_SE + q] = (KIND == 1 && q == p) ? 0.f : ev;      // (kind 1: the diagonal is a constant)
             }
         }
         {
             const int n = tid / SR, pl = tid - n * SR;       // (3 SR <= 512 threads)
             const int p = r0 + pl;
-            if (n < M && n != m && p < L)
+            // (KIND 1: the constant cross entries reach the features through the degrees only -- no ec term)
+            if (KIND == 0 && n < M && n != m && p < L)
                 ec[n * SR + pl] = (pre_dc * rm[p] * rl[n * KS_MAXL + p] + dm[p] + dd[n * KS_MAXL + p]) * modal_weight * ks_dsim(pre_cd);
         }
     }
@@ -654,8 +667,8 @@ __global__ __launch_bounds__(64 * KS_NW) void adj_strip_bwd_kernel(
         float4 du = ok ? *reinterpret_cast<const float4*>(dUl + pl * SD + k4) : make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 uu = ok ? eu[j] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 ad = addend ? ea[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (o0 >= 0) { const float c = ec[o0 * SR + pl]; du.x += c * e0[j].x; du.y += c * e0[j].y; du.z += c * e0[j].z; du.w += c * e0[j].w; }
-        if (o1 >= 0) { const float c = ec[o1 * SR + pl]; du.x += c * e1[j].x; du.y += c * e1[j].y; du.z += c * e1[j].z; du.w += c * e1[j].w; }
+        if (KIND == 0 && o0 >= 0) { const float c = ec[o0 * SR + pl]; du.x += c * e0[j].x; du.y += c * e0[j].y; du.z += c * e0[j].z; du.w += c * e0[j].w; }
+        if (KIND == 0 && o1 >= 0) { const float c = ec[o1 * SR + pl]; du.x += c * e1[j].x; du.y += c * e1[j].y; du.z += c * e1[j].z; du.w += c * e1[j].w; }
         const float s = sum64(dot4(uu, du));
         if (ok) {
             const float inv = 1.0f / einv[j];
@@ -714,17 +727,18 @@ int ks_stop() {
 int mmdfn_launch_adj_small_fwd(const float* feats, float* unit, float* norm, float* cosg, float* cdot, float* rdeg,
                                float* tiles, float* cross, const int32_t* dia_len, const int32_t* row_start,
                                const int64_t* tile_base, int B, int M, int N, int D, int max_len, float modal_weight,
-                               hipStream_t s) {
+                               int kind, hipStream_t s) {
     KsPlan pl;
     if (!ks_plan(B, M, D, max_len, &pl)) return -2;
-#define KS_FWD(SRV)                                                                                                          \
+#define KS_FWD(SRV...)                                                                                                       \
     do {                                                                                                                     \
         if (pl.lds_fwd > 64 * 1024 && mmdfn_allow_big_lds(adj_strip_fwd_kernel<SRV>)) return -2;                            \
-        hipLaunchKernelGGL(adj_strip_fwd_kernel<SRV>, dim3(pl.grid), dim3(64 * KS_NW), pl.lds_fwd, s, feats, unit, norm, cosg, \
+        hipLaunchKernelGGL((adj_strip_fwd_kernel<SRV>), dim3(pl.grid), dim3(64 * KS_NW), pl.lds_fwd, s, feats, unit, norm, cosg, \
                            cdot, rdeg, tiles, cross, dia_len, row_start, tile_base, B, M, N, D, pl.SU, pl.lmax_p, pl.NS,     \
                            modal_weight, ks_stop());                                                                         \
     } while (0)
-    if (pl.SR == 32) KS_FWD(32); else KS_FWD(64);
+    if (kind == 0) { if (pl.SR == 32) KS_FWD(32, 0); else KS_FWD(64, 0); }
+    else { if (pl.SR == 32) KS_FWD(32, 1); else KS_FWD(64, 1); }
 #undef KS_FWD
     MMDFN_CHECK_LAUNCH();
     const int rowblocks = (max_len + 3) / 4;
@@ -739,17 +753,18 @@ int mmdfn_launch_adj_small_bwd(const float* dtiles, const float* dcross, const f
                                const float* cosg, const float* cdot, const float* rdeg, const float* tiles,
                                const float* cross, const float* addend, float* dfeats, const int32_t* dia_len,
                                const int32_t* row_start, const int64_t* tile_base, int B, int M, int N, int D, int max_len,
-                               float modal_weight, hipStream_t s) {
+                               float modal_weight, int kind, hipStream_t s) {
     KsPlan pl;
     if (!ks_plan(B, M, D, max_len, &pl)) return -2;
-#define KS_BWD(SRV)                                                                                                          \
+#define KS_BWD(SRV...)                                                                                                       \
     do {                                                                                                                     \
         if (pl.lds_bwd > 64 * 1024 && mmdfn_allow_big_lds(adj_strip_bwd_kernel<SRV>)) return -2;                            \
-        hipLaunchKernelGGL(adj_strip_bwd_kernel<SRV>, dim3(pl.grid), dim3(64 * KS_NW), pl.lds_bwd, s, dtiles, dcross, unit,   \
+        hipLaunchKernelGGL((adj_strip_bwd_kernel<SRV>), dim3(pl.grid), dim3(64 * KS_NW), pl.lds_bwd, s, dtiles, dcross, unit,   \
                            norm, cosg, cdot, rdeg, tiles, cross, addend, dfeats, dia_len, row_start, tile_base, B, M, N, D,  \
                            pl.SD, pl.NS, modal_weight, ks_stop());                                                           \
     } while (0)
-    if (pl.SR == 32) KS_BWD(32); else KS_BWD(64);
+    if (kind == 0) { if (pl.SR == 32) KS_BWD(32, 0); else KS_BWD(64, 0); }
+    else { if (pl.SR == 32) KS_BWD(32, 1); else KS_BWD(64, 1); }
 #undef KS_BWD
     MMDFN_CHECK_LAUNCH();
     return 0;

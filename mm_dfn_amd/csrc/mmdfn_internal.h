@@ -27,6 +27,30 @@ __device__ __forceinline__ float mmdfn_dsim(float c) {
     return MMDFN_COS_SHRINK / (MMDFN_PI_F * sqrtf(1.0f - ac * ac));
 }
 
+// Graph kinds of the adjacency build (mmdfn_adj_build_kind), a compile-time parameter of its kernels:
+//   0  angular similarity  sim(c) = 1 - acos(0.99999 c) / pi, cross-modal entries sim(cos) * modal_weight
+//      (MM_GCN.create_big_adj, model_mm.py:122-180)
+//   1  arccos distance     sim(c) = acos(0.99999 c), cross-modal entries the constant the modal_weight slot carries
+//      (MM_GCN2.create_big_adj, model_mm.py:241-296; GCNII_lyc.message_passing_wo_speaker, model_GCN.py:490-511)
+//      The diagonal of a tile is cos(x, x) = 1 by definition: kind 1 takes it as that constant (entry acos(0.99999), no
+//      gradient through it) instead of the rounded sum u.u -- acos is at its steepest there (|d acos| = 224 at 0.99999), so
+//      the last-bit noise of a float32 dot product would otherwise be the whole error of the graph (3e-5 against 2e-7).
+constexpr int MMDFN_ADJ_KINDS = 2;
+template <int KIND>
+__device__ __forceinline__ float mmdfn_sim_k(float c) {
+    if (KIND == 0) return mmdfn_sim(c);
+    return acosf(c * MMDFN_COS_SHRINK);
+}
+// kind 1: d acos(a c) / d c = -a / sqrt((1 - a c)(1 + a c)).  The factored radicand keeps its relative accuracy where a c is
+// within 1e-5 of 1 (the diagonal of the Gram matrix, c = 1 +- a few ulp): 1 - a c is exact there, 1 - (a c)^2 would round the
+// square first; it stays positive as long as c < 1 / a = 1 + 1e-5.
+template <int KIND>
+__device__ __forceinline__ float mmdfn_dsim_k(float c) {
+    if (KIND == 0) return mmdfn_dsim(c);
+    const float ac = c * MMDFN_COS_SHRINK;
+    return -MMDFN_COS_SHRINK / sqrtf((1.0f - ac) * (1.0f + ac));
+}
+
 // index of the unordered modality pair (m < n) in lexicographic order
 __host__ __device__ __forceinline__ int mmdfn_pair_index(int m, int n, int M) {
     return m * (2 * M - m - 1) / 2 + (n - m - 1);
@@ -102,12 +126,12 @@ int mmdfn_launch_propagate(const float* tiles, const float* cross, const float* 
 int mmdfn_launch_adj_small_fwd(const float* feats, float* unit, float* norm, float* cosg, float* cdot, float* rdeg,
                                float* tiles, float* cross, const int32_t* dia_len, const int32_t* row_start,
                                const int64_t* tile_base, int B, int M, int N, int D, int max_len, float modal_weight,
-                               hipStream_t s);
+                               int kind, hipStream_t s);
 int mmdfn_launch_adj_small_bwd(const float* dtiles, const float* dcross, const float* unit, const float* norm,
                                const float* cosg, const float* cdot, const float* rdeg, const float* tiles,
                                const float* cross, const float* addend, float* dfeats, const int32_t* dia_len,
                                const int32_t* row_start, const int64_t* tile_base, int B, int M, int N, int D, int max_len,
-                               float modal_weight, hipStream_t s);
+                               float modal_weight, int kind, hipStream_t s);
 
 // bf16-piece variant of the forward product for large launches (propagate_split.hip); -2 = shape not covered
 int mmdfn_launch_propagate_split(const float* tiles, const float* cross, const float* H, float* out,
@@ -131,7 +155,7 @@ int mmdfn_launch_tile_dot_split(const float* X, const float* Y, float* out_tiles
                                 const int32_t* row_start, const int64_t* tile_base, int B, int M, int N, int K, int ldx,
                                 int ldy, int max_len, int accumulate, hipStream_t s);
 
-// EPI 0: dtiles (+)= X.Y^T ; EPI 1: cosine Gram + raw similarity + row degree
+// EPI 0: dtiles (+)= X.Y^T ; EPI 1: cosine Gram + raw similarity + row degree ; EPI 2: EPI 1 with the arccos kind's sim
 int mmdfn_launch_tile_dot(const float* X, const float* Y, float* out_tiles, float* out_aux, float* deg,
                           const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
                           int B, int M, int N, int K, int ldx, int ldy, int max_len, int epi, int accumulate, hipStream_t s);

@@ -6,6 +6,8 @@
 //                  (MN x MN) matrix, model_GCN.py:178).
 //  EPI 1 (gram):   cosine Gram of the unit feature rows + angular similarity
 //                  + row degree (model_mm.py:145-151, 176).
+//  EPI 2 (gram):   the same with the arccos distance of adjacency kind 1
+//                  (model_mm.py:268-270, model_GCN.py:497-499).
 //
 // Both operands are k-contiguous, so both MFMA fragments are loaded straight
 // from global memory with one 16-byte load per lane per 16-wide k-chunk
@@ -82,8 +84,9 @@ __global__ __launch_bounds__(64 * NW) void tile_dot_kernel(
             } else {
                 float s = 0.f;
                 if (ok) {
-                    const float gq = (q < L) ? acc[r] : 0.f;
-                    s = (q < L) ? mmdfn_sim(gq) : 0.f;
+                    float gq = (q < L) ? acc[r] : 0.f;
+                    if (EPI == 2 && q == p) gq = 1.0f;      // (kind 1: cos(x, x) = 1, mmdfn_internal.h)
+                    s = (q < L) ? mmdfn_sim_k<(EPI == 2)>(gq) : 0.f;
                     out_aux[off] = gq;    // raw cosine (saved for backward)
                     out_tiles[off] = s;   // raw similarity; normalised by a later kernel
                 }
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(64 * NW) void tile_dot_kernel(
             }
         }
     }
-    if (EPI == 1 && frow == 0) {
+    if (EPI >= 1 && frow == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int p = r0 + 16 * w + 4 * g + r;
@@ -284,8 +287,12 @@ __global__ __launch_bounds__(256) void tile_dot_v2_kernel(
                     float4 c, sv;
                     c.x = (q + 0 < L) ? v.x : 0.f; c.y = (q + 1 < L) ? v.y : 0.f;
                     c.z = (q + 2 < L) ? v.z : 0.f; c.w = (q + 3 < L) ? v.w : 0.f;
-                    sv.x = (q + 0 < L) ? mmdfn_sim(c.x) : 0.f; sv.y = (q + 1 < L) ? mmdfn_sim(c.y) : 0.f;
-                    sv.z = (q + 2 < L) ? mmdfn_sim(c.z) : 0.f; sv.w = (q + 3 < L) ? mmdfn_sim(c.w) : 0.f;
+                    if (EPI == 2) {                          // (kind 1: cos(x, x) = 1, mmdfn_internal.h)
+                        c.x = (q + 0 == p) ? 1.0f : c.x; c.y = (q + 1 == p) ? 1.0f : c.y;
+                        c.z = (q + 2 == p) ? 1.0f : c.z; c.w = (q + 3 == p) ? 1.0f : c.w;
+                    }
+                    sv.x = (q + 0 < L) ? mmdfn_sim_k<(EPI == 2)>(c.x) : 0.f; sv.y = (q + 1 < L) ? mmdfn_sim_k<(EPI == 2)>(c.y) : 0.f;
+                    sv.z = (q + 2 < L) ? mmdfn_sim_k<(EPI == 2)>(c.z) : 0.f; sv.w = (q + 3 < L) ? mmdfn_sim_k<(EPI == 2)>(c.w) : 0.f;
                     *reinterpret_cast<float4*>(out_aux + off) = c;      // raw cosine (saved for backward)
                     *reinterpret_cast<float4*>(out_tiles + off) = sv;   // raw similarity; normalised later
                     s4 = (sv.x + sv.y) + (sv.z + sv.w);
@@ -300,7 +307,7 @@ __global__ __launch_bounds__(256) void tile_dot_v2_kernel(
         __builtin_amdgcn_wave_barrier();
     }
 #undef TD_TILE
-    if (EPI == 1 && fi == 0) {
+    if (EPI >= 1 && fi == 0) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int p = p0 + g + 4 * e;
@@ -324,8 +331,11 @@ int launch_v2(const float* X, const float* Y, float* out_tiles, float* out_aux, 
         hipLaunchKernelGGL((tile_dot_v2_kernel<KC, 0>), dim3(tile_blocks + (dcross ? (N + 15) / 16 : 0)), dim3(256), 0, s, X, Y,
                            out_tiles, out_aux, deg, dia_len, row_start, tile_base, B, M, N, K, ldx, ldy, max_rb, accumulate,
                            dcross, tile_blocks, qsplit);
-    else
+    else if (epi == 1)
         hipLaunchKernelGGL((tile_dot_v2_kernel<KC, 1>), dim3(tile_blocks), dim3(256), 0, s, X, Y, out_tiles, out_aux, deg,
+                           dia_len, row_start, tile_base, B, M, N, K, ldx, ldy, max_rb, accumulate, nullptr, tile_blocks, 1);
+    else
+        hipLaunchKernelGGL((tile_dot_v2_kernel<KC, 2>), dim3(tile_blocks), dim3(256), 0, s, X, Y, out_tiles, out_aux, deg,
                            dia_len, row_start, tile_base, B, M, N, K, ldx, ldy, max_rb, accumulate, nullptr, tile_blocks, 1);
     MMDFN_CHECK_LAUNCH();
     return 0;
@@ -342,8 +352,11 @@ int launch(const float* X, const float* Y, float* out_tiles, float* out_aux, flo
     if (epi == 0)
         hipLaunchKernelGGL((tile_dot_kernel<NW, KC, 0>), grid, block, 0, s, X, Y, out_tiles, out_aux, deg, dia_len,
                            row_start, tile_base, M, N, K, ldx, ldy, max_rb, accumulate);
-    else
+    else if (epi == 1)
         hipLaunchKernelGGL((tile_dot_kernel<NW, KC, 1>), grid, block, 0, s, X, Y, out_tiles, out_aux, deg, dia_len,
+                           row_start, tile_base, M, N, K, ldx, ldy, max_rb, accumulate);
+    else
+        hipLaunchKernelGGL((tile_dot_kernel<NW, KC, 2>), grid, block, 0, s, X, Y, out_tiles, out_aux, deg, dia_len,
                            row_start, tile_base, M, N, K, ldx, ldy, max_rb, accumulate);
     MMDFN_CHECK_LAUNCH();
     return 0;
@@ -380,7 +393,7 @@ static int launch_tile_dot(const float* X, const float* Y, float* out_tiles, flo
                            const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
                            int B, int M, int N, int K, int ldx, int ldy, int max_len, int epi, int accumulate,
                            hipStream_t s, float** fused_cross) {
-    if (B <= 0 || M <= 0 || N <= 0 || K <= 0 || (K & 3) || max_len <= 0) return -1;
+    if (B <= 0 || M <= 0 || N <= 0 || K <= 0 || (K & 3) || max_len <= 0 || epi < 0 || epi > 2) return -1;
     if (ldx < K || ldy < K || (ldx & 3) || (ldy & 3)) return -1;
 #ifdef MMDFN_TUNING
     const char* sp = getenv("MMDFN_TILEDOT_SPLIT");   // 1 = always the bf16-piece kernel, 0 = never

@@ -84,8 +84,15 @@ class GCNII_lyc(nn.Module):
 
     def forward(self, x, dia_len, topicLabel, adj=None, test_label=False):
         if adj is None:
-            raise NotImplementedError("GCNII_lyc without an explicit adjacency (reference model_GCN.py:490-584) "
-                                      "is outside the MM-DFN hot path; pass adj from MM_GCN.create_big_adj")
+            if self.new_graph:
+                raise NotImplementedError("GCNII_lyc(new_graph=True) without an explicit adjacency "
+                                          "(message_passing_relation_graph, reference model_GCN.py:446-447, :531-584) is a "
+                                          "per-edge Python loop outside the block-tile graph kinds")
+            # message_passing_wo_speaker (model_GCN.py:490-511): the M = 1 arccos graph, normalised per dialogue -- on a
+            # block-diagonal matrix that is D^-1/2 A D^-1/2 of the whole
+            _hip.require_cuda(x)
+            adj = ops.build_adjacency(x.unsqueeze(0), [int(n) for n in dia_len], kind='arccos')
+            x = adj.stacked_feats[0]                  # the tensor the adjacency gradient flows back through
         _hip.require_cuda(x)                          # MI355X path only: no CPU fallback
         fused = isinstance(adj, BlockTileAdjacency) and all(c.variant and not c.residual for c in self.convs)
         dump = self._dump_layer if test_label else None

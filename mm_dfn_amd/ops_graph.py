@@ -68,9 +68,13 @@ def propagate(adj, H):
     return _Propagate.apply(adj.tiles, adj.cross, H, adj.layout, adj.symmetric)
 
 
+# graph kinds of the adjacency build (include/mmdfn_hip.h mmdfn_adj_build_kind)
+ADJ_KINDS = {"angular": 0, "arccos": 1}
+
+
 class _BuildAdjacency(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats_in, lay, modal_weight):
+    def forward(ctx, feats_in, lay, modal_weight, kind):
         _hip.require_cuda(feats_in)
         feats = feats_in.contiguous()
         M, N, D = feats.shape
@@ -83,12 +87,13 @@ class _BuildAdjacency(torch.autograd.Function):
         rdeg = torch.empty(M, N, **f32)
         tiles = torch.empty(lay.tile_elems, **f32)
         cross = torch.empty(lay.npairs, N, **f32)
-        rc = _hip.lib().mmdfn_adj_build(_hip.ptr(feats), _hip.ptr(unit), _hip.ptr(norm), _hip.ptr(cosg),
-                                        _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles), _hip.ptr(cross),
-                                        *_lay_args(lay), lay.B, M, N, D, lay.max_len, float(modal_weight),
-                                        _hip.stream())
-        _hip.check(rc, "mmdfn_adj_build")
+        rc = _hip.lib().mmdfn_adj_build_kind(_hip.ptr(feats), _hip.ptr(unit), _hip.ptr(norm), _hip.ptr(cosg),
+                                             _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles), _hip.ptr(cross),
+                                             *_lay_args(lay), lay.B, M, N, D, lay.max_len, float(modal_weight),
+                                             int(kind), _hip.stream())
+        _hip.check(rc, "mmdfn_adj_build_kind")
         ctx.lay = lay
+        ctx.kind = int(kind)
         ctx.modal_weight = float(modal_weight)
         ctx.save_for_backward(unit, norm, cosg, cdot, rdeg, tiles, cross)
         ctx.set_materialize_grads(False)
@@ -100,7 +105,7 @@ class _BuildAdjacency(torch.autograd.Function):
     def backward(ctx, dtiles, dcross, dalias):
         unit, norm, cosg, cdot, rdeg, tiles, cross = ctx.saved_tensors
         if dtiles is None and dcross is None:
-            return dalias, None, None
+            return dalias, None, None, None
         lay = ctx.lay
         M, N, D = unit.shape
         f32 = dict(dtype=torch.float32, device=unit.device)
@@ -113,27 +118,33 @@ class _BuildAdjacency(torch.autograd.Function):
         dunit = torch.empty_like(unit)
         dfeats = torch.empty_like(unit)
         addend = dalias.contiguous() if dalias is not None else None
-        rc = _hip.lib().mmdfn_adj_build_bwd(_hip.ptr(dtiles), _hip.ptr(dcross), _hip.ptr(unit), _hip.ptr(norm),
-                                            _hip.ptr(cosg), _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles),
-                                            _hip.ptr(cross), _hip.ptr(wsym), _hip.ptr(etile), _hip.ptr(ecross),
-                                            _hip.ptr(ddeg), _hip.ptr(dunit), _hip.ptr(dfeats), _hip.ptr(addend),
-                                            *_lay_args(lay),
-                                            lay.B, M, N, D, lay.max_len, ctx.modal_weight, _hip.stream())
-        _hip.check(rc, "mmdfn_adj_build_bwd")
+        rc = _hip.lib().mmdfn_adj_build_bwd_kind(_hip.ptr(dtiles), _hip.ptr(dcross), _hip.ptr(unit), _hip.ptr(norm),
+                                                 _hip.ptr(cosg), _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles),
+                                                 _hip.ptr(cross), _hip.ptr(wsym), _hip.ptr(etile), _hip.ptr(ecross),
+                                                 _hip.ptr(ddeg), _hip.ptr(dunit), _hip.ptr(dfeats), _hip.ptr(addend),
+                                                 *_lay_args(lay),
+                                                 lay.B, M, N, D, lay.max_len, ctx.modal_weight, ctx.kind, _hip.stream())
+        _hip.check(rc, "mmdfn_adj_build_bwd_kind")
         # the graph part of the backward pass ends here (the encoders' nodes follow): its queued weight gradients leave now
         flush_queued_wgrads_early()
-        return dfeats, None, None
+        return dfeats, None, None, None
 
 
-def build_adjacency(feats, lengths, modal_weight=1.0):
+def build_adjacency(feats, lengths, modal_weight=1.0, kind="angular"):
     """feats: (M, N, D) stacked modality features -> BlockTileAdjacency
-    (reference: MM_GCN.create_big_adj, model_mm.py:122-180)."""
+    (reference: MM_GCN.create_big_adj, model_mm.py:122-180).
+
+    kind='arccos': the graph of the MMGCN baseline (MM_GCN2.create_big_adj, model_mm.py:260-296) and, with M = 1, of
+    GCNII_lyc.message_passing_wo_speaker (model_GCN.py:490-511): edge weight acos(0.99999 cos) in radians within a modality,
+    the constant ``modal_weight`` between the modalities of one utterance (MM_GCN2 uses 0.99999)."""
+    if kind not in ADJ_KINDS:
+        raise ValueError("build_adjacency: kind must be one of %s (got %r)" % (sorted(ADJ_KINDS), kind))
     lay = DialogueLayout.get(lengths, feats.shape[0], feats.device)
     if lay.N != feats.shape[1]:
         raise ValueError("sum(dia_len)=%d does not match %d feature rows" % (lay.N, feats.shape[1]))
     if feats.shape[2] % 4:
         raise ValueError("feature width must be a multiple of 4 for the HIP path")
-    tiles, cross, feats = _BuildAdjacency.apply(feats, lay, modal_weight)
+    tiles, cross, feats = _BuildAdjacency.apply(feats, lay, modal_weight, ADJ_KINDS[kind])
     return BlockTileAdjacency(lay, tiles, cross, symmetric=True, stacked_feats=feats)
 
 
