@@ -47,7 +47,8 @@ extern "C" {
 int64_t mmdfn_riders_bytes(void);
 
 /* Library / device sanity: returns the ABI version (currently 23: 22 + the graph kind of the adjacency build mmdfn_adj_build_kind,
- * mmdfn_adj_build_bwd_kind; 22 = 21 + FlatAdam on device-resident step state mmdfn_adam_state_bytes, mmdfn_grad_sumsq,
+ * mmdfn_adj_build_bwd_kind, and -- an addition that moves no existing symbol, so 23 also carries it -- the key-band builder of the
+ * sparse graphs mmdfn_adj_build_band; 22 = 21 + FlatAdam on device-resident step state mmdfn_adam_state_bytes, mmdfn_grad_sumsq,
  * mmdfn_adam_prepare, mmdfn_adam_step_state; 21 = 20 + the TFN tensor-fusion kernels mmdfn_tfn_{workspace,fwd,bwd_input,bwd_weight,keep_flags};
  * 20 = 19 + mmdfn_linear_planes_group_in (input dropout in the
  * plane projection's staging step), mmdfn_linear_planes_group_party (party-ordered store) and mmdfn_linear_group_seg2 (two K segments per few-row problem); 19 = 18 + the head without its ReLU mmdfn_head_{fwd,bwd,bwd_partial}_act
@@ -140,6 +141,30 @@ int mmdfn_adj_build_bwd_kind(const float* dtiles, const float* dcross,
                              float* dfeats, const float* addend,
                              const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
                              int B, int M, int N, int D, int max_len, float modal_weight, int kind, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K5b  the sparse unimodal graphs of GCNII / GCNII_lyc with new_graph=True (csrc/adjacency_band.hip): the context window
+ * of message_passing_relation_graph (model_GCN.py:381-409, :556-584) and the speaker chains of
+ * message_passing_directed_speaker (model_GCN.py:348-379, :523-554).  Forward only: the reference takes every edge weight
+ * through math.acos on a Python float, so the graph is a constant for autograd.
+ *   feats : (N, D) fp32, D % 4 == 0;  M must be 1
+ *   keys  : (N) int32, one per row: rank in the low 24 bits, chain in the bits above (key = chain << 24 | rank, both >= 0).
+ *           Rows p != q of ONE dialogue are joined iff chain_p == chain_q and |rank_p - rank_q| <= width.
+ *             window graph   : chain 0, rank = position in the dialogue, width 20 (the union of the reference's
+ *                              [k - 10, k + 10] cliques)
+ *             speaker chains : chain 0 where qmask[i][j][0] == 1, chain 1 otherwise; rank = index inside the chain; width 1
+ *   on an edge  S[p,q] = 1 - acos(c) / pi,  c = x_p.x_q / (||x_p|| ||x_q||) clamped to [-1, 1], taken as 0 when either norm is
+ *               0 (weight 0.5; no x / 0 is formed); there is no 0.99999 shrink
+ *   S[p,p] = 1 (a constant, not a dot product), S = 0 elsewhere;  degree = row sum of S (>= 1)
+ *   deg   : (N) scratch, the degrees;  rdeg : (N) out, degree^-1/2 (always finite)
+ *   tiles : out, (r_p S[p,q]) r_q in the block-tile layout above as DENSE dia_len[i] x ld_i tiles: entries that are no
+ *           edge and the pad columns are written as exact 0.0f.  Dot products are formed for the pairs of the predicate
+ *           only: O(N width D) work.  There are no cross diagonals (M = 1).
+ *   Returns -1 before any launch for width < 0, M != 1, D % 4 != 0, non-positive sizes or a null pointer.
+ * ------------------------------------------------------------------------- */
+int mmdfn_adj_build_band(const float* feats, const int32_t* keys, float* deg, float* rdeg, float* tiles,
+                         const int32_t* dia_len, const int32_t* row_start, const int64_t* tile_base,
+                         int B, int M, int N, int D, int max_len, int width, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K2  fused GRU recurrence (replaces the time loop inside nn.GRU for ``lstm_l``

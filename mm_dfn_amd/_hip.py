@@ -24,6 +24,7 @@ SIGNATURES = {
     "mmdfn_adj_build_bwd": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
     "mmdfn_adj_build_kind": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
     "mmdfn_adj_build_bwd_kind": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
+    "mmdfn_adj_build_band": [_P] * 5 + [_P, _P, _P] + [_I] * 6 + [_P],
     "mmdfn_riders_bytes": [],
     "mmdfn_gru_seq_fwd": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "mmdfn_gru_seq_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],

@@ -85,9 +85,9 @@ class GCNII_lyc(nn.Module):
     def forward(self, x, dia_len, topicLabel, adj=None, test_label=False):
         if adj is None:
             if self.new_graph:
-                raise NotImplementedError("GCNII_lyc(new_graph=True) without an explicit adjacency "
-                                          "(message_passing_relation_graph, reference model_GCN.py:446-447, :531-584) is a "
-                                          "per-edge Python loop outside the block-tile graph kinds")
+                raise NotImplementedError("GCNII_lyc(new_graph=True) without an explicit adjacency (reference "
+                                          "model_GCN.py:446-447) is not built inside forward: build the window graph with "
+                                          "self.message_passing_relation_graph(x, dia_len) and pass it as adj=")
             # message_passing_wo_speaker (model_GCN.py:490-511): the M = 1 arccos graph, normalised per dialogue -- on a
             # block-diagonal matrix that is D^-1/2 A D^-1/2 of the whole
             _hip.require_cuda(x)
@@ -97,6 +97,25 @@ class GCNII_lyc(nn.Module):
         fused = isinstance(adj, BlockTileAdjacency) and all(c.variant and not c.residual for c in self.convs)
         dump = self._dump_layer if test_label else None
         return self._forward_fused(x, adj, dump) if fused else self._forward_generic(x, adj, dump)
+
+    # the two sparse graphs of new_graph=True, under the reference's names and arguments (model_GCN.py:523-584; GCNII has the
+    # same two, :348-409).  Both return a BlockTileAdjacency that forward(..., adj=adj) takes; they are constants for autograd
+    # (the reference computes every weight with math.acos on a Python float).
+    window_size = 10
+
+    def message_passing_relation_graph(self, x, dia_len):
+        """Context window: the reference joins all pairs inside [k - window_size, k + window_size] for every k; the union of
+        those cliques is the band |p - q| <= 2 window_size."""
+        _hip.require_cuda(x)
+        lengths = [int(n) for n in dia_len]
+        return ops.build_band_adjacency(x, lengths, ops.window_keys(lengths, x.device), 2 * self.window_size)
+
+    def message_passing_directed_speaker(self, x, dia_len, qmask):
+        """Speaker chains: every utterance is joined to the previous and the next one of its own chain (chain 0: speaker 0,
+        chain 1: everyone else).  qmask: (dialogue, position, speaker)."""
+        _hip.require_cuda(x, qmask)
+        lengths = [int(n) for n in dia_len]
+        return ops.build_band_adjacency(x, lengths, ops.speaker_keys(qmask, lengths), 1)
 
     # the reference's --test_label activation dump (model_GCN.py:474-480): every layer's output (after dropout and the
     # residual q) is printed and saved as <test_output_dir>/1080_v1_test_output_layer_<i>.npy.  The dump needs the
@@ -225,10 +244,12 @@ class GCNII(GCNII_lyc):
 
     def forward(self, x, dia_len, qmask=None):
         if self.new_graph:
-            raise NotImplementedError("GCNII(new_graph=True) (speaker-directed message passing, model_GCN.py:312-411) "
-                                      "is outside the MM-DFN hot path")
-        _hip.require_cuda(x)
-        adj = self.create_big_adj(x, dia_len)
-        x = adj.stacked_feats[0]            # the tensor the adjacency gradient flows back through
+            if qmask is None:
+                raise ValueError("GCNII(new_graph=True) builds the speaker-chain graph (model_GCN.py:257-258): it needs qmask")
+            adj = self.message_passing_directed_speaker(x, dia_len, qmask)      # a constant: no gradient path through it
+        else:
+            _hip.require_cuda(x)
+            adj = self.create_big_adj(x, dia_len)
+            x = adj.stacked_feats[0]            # the tensor the adjacency gradient flows back through
         fused = all(c.variant and not c.residual for c in self.convs)
         return self._forward_fused(x, adj) if fused else self._forward_generic(x, adj.to_dense())

@@ -14,7 +14,8 @@ from .ops_pad import (  # noqa: F401
 )
 from .ops_graph import (  # noqa: F401
     propagate_raw, tile_outer_raw, _Propagate, propagate, _BuildAdjacency, build_adjacency, _PropagateConcat,
-    propagate_concat, _LstmPointwise, lstm_pointwise, _GcniiCombine, gcnii_combine,
+    propagate_concat, _LstmPointwise, lstm_pointwise, _GcniiCombine, gcnii_combine, window_keys, speaker_keys,
+    build_band_adjacency,
 )
 from .ops_wgrad import (  # noqa: F401
     colsum, _strided_rows, gemm_tn_supported, gemm_tn, gemm_tn_grouped, _WGQ, EARLY_WGRAD, _WG_MAX, wgrad_batch,

@@ -3,10 +3,11 @@
 Part of the operator layer over the C-ABI kernels (libmmdfn_hip.so); `mm_dfn_amd.ops` re-exports every name.
 Every function launches hand-written gfx950 kernels on the current HIP stream; there is no CPU / eager fallback.
 """
+import numpy as np
 import torch
 
 from . import _hip
-from .layout import BlockTileAdjacency, DialogueLayout
+from .layout import _LAYOUT_CACHE, BlockTileAdjacency, DialogueLayout, IndexScope
 from .ops_pad import _lay_args, _rows_view
 from .ops_wgrad import flush_queued_wgrads_early
 
@@ -146,6 +147,91 @@ def build_adjacency(feats, lengths, modal_weight=1.0, kind="angular"):
         raise ValueError("feature width must be a multiple of 4 for the HIP path")
     tiles, cross, feats = _BuildAdjacency.apply(feats, lay, modal_weight, ADJ_KINDS[kind])
     return BlockTileAdjacency(lay, tiles, cross, symmetric=True, stacked_feats=feats)
+
+
+# ---- the sparse graphs of new_graph=True (K5b, csrc/adjacency_band.hip) -------------------------------------------------------
+BAND_RANK_BITS = 24       # key = chain << 24 | rank (include/mmdfn_hip.h mmdfn_adj_build_band)
+
+
+def _length_index(name, lengths, maker, device):
+    """Device index tensor that depends on the dialogue lengths only -- the cached path of dialogue_model._flat_index: a
+    captured step replayed for other length lists (IndexScope) owns and rewrites its own copy, everything else shares an
+    LRU entry (the layout cache's, whose entries graphs.CapturedStep keeps alive for the graphs that baked their addresses)."""
+    lengths = [int(n) for n in lengths]
+    scope = IndexScope.current()
+    if scope is not None:
+        return scope.tensor((name, str(device)), lengths, maker, device)
+    return _LAYOUT_CACHE.get((name, tuple(lengths), str(device)), lambda: torch.from_numpy(maker(lengths)).to(device))
+
+
+def _positions(lens):
+    lens = np.asarray([int(n) for n in lens], dtype=np.int64)
+    return np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+
+
+def window_keys(lengths, device):
+    """(N,) int32 keys of the context-window graph (message_passing_relation_graph): chain 0, rank = position in the dialogue."""
+    return _length_index("window_keys", lengths, lambda lens: _positions(lens).astype(np.int32), device)
+
+
+def speaker_keys(qmask, lengths):
+    """(N,) int32 keys of the speaker-chain graph (message_passing_directed_speaker, model_GCN.py:348-379).  qmask: (dialogue,
+    position, speaker), as the reference's ``qmask[i][0:len_]`` reads it; utterance j of dialogue i is in chain 0 where
+    ``qmask[i][j][0] == 1`` and in chain 1 otherwise (however many speakers), its rank is its index inside the chain.
+    Positions >= len_ are never read.  Device tensor operations only (no host read of qmask): a captured step recomputes the
+    keys from the static qmask tensor on every replay.  (Plain tensor operations: they run wherever qmask lives; the builder
+    that takes the keys is the device-only part.)"""
+    lengths = [int(n) for n in lengths]
+    if qmask.dim() != 3 or qmask.shape[0] < len(lengths) or qmask.shape[1] < max(lengths):
+        raise ValueError("speaker_keys: qmask must be (dialogue, position, speaker) covering dia_len (got %s)"
+                         % (tuple(qmask.shape),))
+    Lmax = int(qmask.shape[1])
+
+    def index(lens):          # rows: the (dialogue, position) slot of every utterance in qmask; the first row of its dialogue
+        lens = np.asarray([int(n) for n in lens], dtype=np.int64)
+        start = np.repeat(np.cumsum(lens) - lens, lens)
+        return np.stack([np.repeat(np.arange(lens.size, dtype=np.int64), lens) * Lmax + _positions(lens), start])
+    slot, first = _length_index("speaker_index%d" % Lmax, lengths, index, qmask.device)
+    pos = window_keys(lengths, qmask.device)
+    is0 = (qmask[:, :, 0].reshape(-1)[slot] == 1).to(torch.int32)
+    before = torch.cumsum(is0, 0, dtype=torch.int32) - is0      # chain-0 utterances in front of this one ...
+    before = before - before[first]                             # ... inside its own dialogue
+    rank = torch.where(is0 == 1, before, pos - before)
+    return (((1 - is0) << BAND_RANK_BITS) | rank).to(torch.int32)
+
+
+def build_band_adjacency(x, lengths, keys, width):
+    """x: (N, D) features, keys: (N,) int32 (window_keys / speaker_keys) -> BlockTileAdjacency of the unimodal graph that joins
+    rows p != q of one dialogue iff their chains are equal and |rank_p - rank_q| <= width, with edge weight
+    1 - acos(cos(x_p, x_q)) / pi, unit diagonal, D^-1/2 S D^-1/2 (reference: message_passing_relation_graph with width 20,
+    message_passing_directed_speaker with width 1).  The graph is a constant for autograd, as in the reference (math.acos on
+    Python floats): its tiles never require grad, so nothing downstream forms an adjacency gradient.  ``adj.rdeg``: (N,)
+    degree^-1/2."""
+    _hip.require_cuda(x, keys)
+    _hip.require_f32(x)
+    if x.dim() != 2:
+        raise ValueError("build_band_adjacency: features must be (N, D)")
+    lay = DialogueLayout.get(lengths, 1, x.device)
+    N, D = x.shape
+    if lay.N != N:
+        raise ValueError("sum(dia_len)=%d does not match %d feature rows" % (lay.N, N))
+    if D % 4:
+        raise ValueError("feature width must be a multiple of 4 for the HIP path")
+    if keys.dtype != torch.int32 or tuple(keys.shape) != (N,):
+        raise ValueError("build_band_adjacency: keys must be an int32 tensor of %d entries" % N)
+    if int(width) < 0:
+        raise ValueError("build_band_adjacency: width must be >= 0")
+    feats = x.detach().contiguous()
+    keys = keys.contiguous()
+    f32 = dict(dtype=torch.float32, device=x.device)
+    deg, rdeg = torch.empty(N, **f32), torch.empty(N, **f32)
+    tiles = torch.empty(lay.tile_elems, **f32)
+    rc = _hip.lib().mmdfn_adj_build_band(_hip.ptr(feats), _hip.ptr(keys), _hip.ptr(deg), _hip.ptr(rdeg), _hip.ptr(tiles),
+                                         *_lay_args(lay), lay.B, 1, N, D, lay.max_len, int(width), _hip.stream())
+    _hip.check(rc, "mmdfn_adj_build_band")
+    adj = BlockTileAdjacency(lay, tiles, torch.empty(0, N, **f32), symmetric=True)
+    adj.rdeg = rdeg
+    return adj
 
 
 class _PropagateConcat(torch.autograd.Function):
