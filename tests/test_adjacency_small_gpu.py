@@ -98,7 +98,8 @@ def test_strip_form_matches_the_many_launch_form(lengths, M, D, sr, kernel_varia
     ref2 = _buffers(lay, M, N, D, 7)
     _run(ref2, lay, M, N, D, 0.7, addend=False)
     # (the adjacency gradient alone: both forms sit 2-5e-5 from an fp64 evaluation -- the fp32 forward's acos near the unit
-    # diagonal -- and so up to that far from each other; tools/adj_forms_vs_f64.py prints the two errors side by side)
+    # diagonal -- and so up to that far from each other; tests/test_angular_graph_gpu.py holds each form to float64 and prints
+    # the distance between them on correlated and duplicated rows, where it is larger)
     assert rel_err(got2["dfeats"], ref2["dfeats"]) < 6e-5
 
 

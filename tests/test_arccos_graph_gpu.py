@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from angular_graph_ref import (EPS_HALF, KIND1_FAMILIES, KIND1_SEED, SHRINK, dense_from, err, make_feats, pack_tiles, pool_perms,
+                               written_mask)
 from mm_dfn_amd import GCNII_lyc, MM_GCN2, _hip, ops, ops_flags
 from mm_dfn_amd.layout import DialogueLayout, pair_list
 from mm_dfn_amd.ops_pad import _lay_args
@@ -30,13 +32,13 @@ from mm_dfn_amd.ops_pad import _lay_args
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SHRINK = float(np.float32(0.99999))          # the float32 constant the kernels and the reference's float32 tensors multiply by
-EPS_HALF = 2.0 ** -24
 
 
 # ---- restatements (dtype-generic, CPU) ---------------------------------------------------------------------------------------------
-def graph_ref(feats, lengths, c):
-    """Arccos graph of (M, N, D) features: per-dialogue normalised tiles [(M, L, L)], cross (npairs, N), rdeg (M, N), unit."""
+def graph_ref(feats, lengths, c, unit_diagonal=False):
+    """Arccos graph of (M, N, D) features: per-dialogue normalised tiles [(M, L, L)], cross (npairs, N), rdeg (M, N), unit.
+    unit_diagonal: cos(x, x) is the constant 1, as the kernels define it (mmdfn_internal.h), not the rounded sum u.u -- the
+    same value in float64 to 1e-12, in float32 an evaluation without the diagonal's 3e-5 of acos noise."""
     M, N, D = feats.shape
     c = float(np.float32(c))
     norm = (feats * feats).sum(-1).sqrt()
@@ -46,7 +48,10 @@ def graph_ref(feats, lengths, c):
     S, deg, s = [], [], 0
     for L in lengths:
         u = unit[:, s:s + L]
-        Si = torch.acos(SHRINK * (u @ u.transpose(1, 2)))
+        G = u @ u.transpose(1, 2)
+        if unit_diagonal:
+            G = torch.where(torch.eye(L, dtype=torch.bool), torch.ones_like(G), G)
+        Si = torch.acos(SHRINK * G)
         S.append(Si)
         deg.append(Si.sum(-1) + (M - 1) * c)
         s += L
@@ -61,45 +66,12 @@ def graph_ref(feats, lengths, c):
     return dict(tiles=tiles, cross=cross, rdeg=rdeg, unit=unit, norm=norm)
 
 
-def pack_tiles(lay, tiles, M):
-    """[(M, L, L)] -> the flat block-tile array (pad columns 0)."""
-    flat = tiles[0].new_zeros(lay.tile_elems)
-    for i, L in enumerate(lay.lengths):
-        ld, base = int(lay.ld_host[i]), int(lay.tile_base_host[i])
-        blk = tiles[i].new_zeros(M, L, ld)
-        blk[:, :, :L] = tiles[i]
-        flat[base:base + M * L * ld] = blk.reshape(-1)
-    return flat
-
-
-def dense_from(g, lengths, M, N):
-    A = g["cross"].new_zeros(M * N, M * N)
-    s = 0
-    for L, T in zip(lengths, g["tiles"]):
-        for m in range(M):
-            A[m * N + s:m * N + s + L, m * N + s:m * N + s + L] = T[m]
-        s += L
-    ar = torch.arange(N)
-    for k, (m, n) in enumerate(pair_list(M)):
-        A[m * N + ar, n * N + ar] = g["cross"][k]
-        A[n * N + ar, m * N + ar] = g["cross"][k]
-    return A
-
-
-def written_mask(lay, M):
-    mask = torch.zeros(lay.tile_elems, dtype=torch.bool)
-    for i, L in enumerate(lay.lengths):
-        ld, base = int(lay.ld_host[i]), int(lay.tile_base_host[i])
-        mask[base:base + M * L * ld] = True
-    return mask
-
-
-def graph_eval(feats, lengths, c, dtiles, dcross, addend, dtype):
+def graph_eval(feats, lengths, c, dtiles, dcross, addend, dtype, unit_diagonal=False):
     """tiles / cross / rdeg / dfeats (without and with the addend) of the restatement in ``dtype`` on the CPU."""
     M, N, D = feats.shape
     lay = DialogueLayout.get(lengths, M, torch.device("cpu"))
     x = feats.to(dtype).requires_grad_(True)
-    g = graph_ref(x, lengths, c)
+    g = graph_ref(x, lengths, c, unit_diagonal)
     flat = pack_tiles(lay, g["tiles"], M)
     ((flat * dtiles.to(dtype)).sum() + (g["cross"] * dcross.to(dtype)).sum()).backward()
     du = (g["unit"].grad / g["norm"][..., None]).detach()
@@ -107,13 +79,25 @@ def graph_eval(feats, lengths, c, dtiles, dcross, addend, dtype):
                 dfeats_add=x.grad + addend.to(dtype), du=du)
 
 
-def err(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return float((got - want).abs().max() / want.abs().max())
+def graph_eval_pooled(feats, lengths, c, dtiles, dcross, addend, r64, perms, unit_diagonal=True):
+    """{quantity: the largest error against ``r64`` of float32 evaluations with the feature columns in each order of ``perms``}
+    -- the pooled yardstick of angular_graph_ref.py, for inputs on which one float32 evaluation is not a stable measure."""
+    yard = {}
+    for perm in perms:
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(len(perm))
+        r = graph_eval(feats.detach()[..., perm].contiguous(), lengths, c, dtiles, dcross, addend[..., perm].contiguous(), torch.float32,
+                       unit_diagonal)
+        for k in ("tiles", "cross", "rdeg", "dfeats", "dfeats_add"):
+            v = r[k][..., inv] if k.startswith("dfeats") else r[k]
+            if v.numel():
+                yard[k] = max(yard.get(k, EPS_HALF), err(v, r64[k]))
+    return yard
 
 
 def check(name, got, want64, want32, lines=None):
-    e, e32 = err(got, want64), err(want32, want64)
+    """want32: the float32 CPU evaluation, or its error against ``want64`` already (a pooled yardstick)."""
+    e, e32 = err(got, want64), want32 if isinstance(want32, float) else err(want32, want64)
     ratio = e / max(e32, EPS_HALF)
     msg = "%-28s kernel %.3e  float32 CPU %.3e  ratio %.2f" % (name, e, e32, ratio)
     print(msg)
@@ -175,9 +159,33 @@ GENERAL = [([129, 4], 3, 200), ([5, 1, 3], 3, 260), ([9, 2], 6, 64)]
 
 @pytest.mark.parametrize("lengths,M,D,form", [s + ("strip",) for s in STRIP] + [s + ("general",) for s in GENERAL])
 def test_kind1_kernels_against_float64(lengths, M, D, form):
+    kind1_against_float64(lengths, M, D, form)
+
+
+# Structured features (angular_graph_ref.make_feats): kind 1 takes its diagonal as a constant, so its only ill-conditioned entries
+# are off-diagonal cosines of +-1 -- correlated rows, exact duplicates, exact opposites -- and rows whose norms span 24 decades.
+STRUCTURED = [(([33, 1, 32], 3, 200), "strip"), (([129, 4], 3, 200), "general")]
+
+
+@pytest.mark.parametrize("family", KIND1_FAMILIES)
+@pytest.mark.parametrize("shape,form", STRUCTURED, ids=["strip", "general"])
+def test_kind1_kernels_against_float64_on_structured_features(shape, form, family):
+    """Measured against the pooled yardstick of float32 evaluations that take the diagonal as the constant the kernels take.  One
+    float32 evaluation with the rounded u.u on its diagonal, the yardstick of the test above, is no stable measure here: other
+    column orders sit up to 450 x its error, and where the off-diagonal entries are well conditioned (scale) it is 100 x what
+    float32 arithmetic gives on the entries the kernels do compute (test_angular_graph_host.py prints both).
+    Worst measured kernel / yardstick (MI355X): strip form tiles 1.20, cross 1.30, rdeg 1.12, dfeats 1.10; many-launch form tiles
+    2.61, cross 2.10, rdeg 1.43, dfeats 1.09."""
+    lengths, M, D = shape
+    kind1_against_float64(lengths, M, D, form, make_feats(family, M, sum(lengths), D, KIND1_SEED), family + " ", pooled=True)
+
+
+def kind1_against_float64(lengths, M, D, form, feats=None, note="", pooled=False):
     N, c = sum(lengths), 0.99999
     lay = DialogueLayout.get(lengths, M, torch.device(DEV))
     b = buffers(lay, M, N, D, 11 + N + M)
+    if feats is not None:
+        b["feats"] = feats.to(DEV)
     names = kernel_names(lambda: run_entry(b, lay, M, N, D, c, 1, True))
     strip = any("adj_strip_fwd_kernel" in n for n in names)
     print("kernels:", sorted(n.replace("void (anonymous namespace)::", "").split("(")[0] for n in names if "kernel" in n))
@@ -187,13 +195,15 @@ def test_kind1_kernels_against_float64(lengths, M, D, form):
         assert not strip and not any("adj_strip_bwd_kernel" in n for n in names), names
         assert any("tile_dot" in n for n in names) and any("bwd_etile_kernel" in n for n in names), names
     cpu = {k: b[k].cpu() for k in ("feats", "dtiles", "dcross", "addend")}
-    r64 = graph_eval(cpu["feats"], lengths, c, cpu["dtiles"], cpu["dcross"], cpu["addend"], torch.float64)
-    r32 = graph_eval(cpu["feats"], lengths, c, cpu["dtiles"], cpu["dcross"], cpu["addend"], torch.float32)
+    r64 = graph_eval(cpu["feats"], lengths, c, cpu["dtiles"], cpu["dcross"], cpu["addend"], torch.float64, pooled)
+    r32 = graph_eval(cpu["feats"], lengths, c, cpu["dtiles"], cpu["dcross"], cpu["addend"], torch.float32, pooled)
+    if pooled:
+        r32 = dict(r32, **graph_eval_pooled(cpu["feats"], lengths, c, cpu["dtiles"], cpu["dcross"], cpu["addend"], r64, pool_perms(D)))
     w = written_mask(lay, M)
     tiles = b["tiles"].cpu()
     assert not torch.isnan(tiles[w]).any()             # every stored entry and every pad column is written
-    tag = "%s M=%d D=%d " % (lengths, M, D)
-    check(tag + "tiles", tiles[w], r64["tiles"][w], r32["tiles"][w])
+    tag = "%s%s M=%d D=%d " % (note, lengths, M, D)
+    check(tag + "tiles", tiles[w], r64["tiles"][w], r32["tiles"] if pooled else r32["tiles"][w])
     pad = r64["tiles"][w] == 0                          # (a stored entry is an acos of less than 1: never 0)
     if bool(pad.any()):
         assert float(tiles[w][pad].abs().max()) == 0.0
