@@ -5,124 +5,60 @@ an error, the product path raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 from . import build as _build
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
 _F = ctypes.c_float
-_L = ctypes.c_int64
 
-# name -> argtypes; must list every symbol of include/mmdfn_hip.h
-SIGNATURES = {
-    "mmdfn_abi_version": [],
-    "mmdfn_propagate": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_tile_outer": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_adj_build": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
-    "mmdfn_adj_build_bwd": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _P],
-    "mmdfn_adj_build_kind": [_P] * 8 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
-    "mmdfn_adj_build_bwd_kind": [_P] * 16 + [_P, _P, _P] + [_I] * 5 + [_F, _I, _P],
-    "mmdfn_adj_build_band": [_P] * 5 + [_P, _P, _P] + [_I] * 6 + [_P],
-    "mmdfn_riders_bytes": [],
-    "mmdfn_gru_seq_fwd": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "mmdfn_gru_seq_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "mmdfn_gru_seq_fwd_seg": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
-    "mmdfn_gru_seq_bwd_seg": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_gru_tab_reduce": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "mmdfn_lstm_pointwise_fwd": [_P, _P, _P, _P, _L, _I, _P],
-    "mmdfn_lstm_pointwise_bwd": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
-    "mmdfn_gcnii_combine_fwd": [_P, _P, _P, _P, _P, _F, _F, _L, _I, _P],
-    "mmdfn_gcnii_combine_bwd": [_P, _P, _P, _P, _P, _P, _F, _F, _L, _I, _P],
-    "mmdfn_gcn_input_fwd": [_P] * 8 + [_I] * 4 + [_F, _P],
-    "mmdfn_gcn_input_bwd": [_P] * 9 + [_I] * 4 + [_F, _P],
-    "mmdfn_lstm_gate_fwd": [_P] * 10 + [_I] * 2 + [_P],
-    "mmdfn_lstm_gate_fwd_ld": [_P] * 10 + [_I] * 3 + [_P],
-    "mmdfn_lstm_gate_fwd_pre": [_P] * 10 + [_I] * 3 + [_P, _P],
-    "mmdfn_lstm_gate_planes_workspace": [_I],
-    "mmdfn_lstm_gate_cut_weights": [_P, _P, _P, _I, _P],
-    "mmdfn_lstm_gate_takes_planes": [_I, _I],
-    "mmdfn_lstm_gate_bwd": [_P] * 13 + [_I] * 4 + [_P],
-    "mmdfn_gcnii_layer_fwd": [_P] * 7 + [_F, _F, _I, _I, _I, _F, _P],
-    "mmdfn_prop_layer_fwd": [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _F, _P],
-    "mmdfn_gcnii_layer_bwd": [_P] * 6 + [_F, _F, _I, _I, _I, _I, _P],
-    "mmdfn_gcnii_layer_bwd_ld": [_P] * 6 + [_F, _F, _I, _I, _I, _I, _I, _P],
-    "mmdfn_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_linear2": [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_weight_planes_workspace": [_I, _I],
-    "mmdfn_cut_weight_planes": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_linear_planes": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_linear_planes_group": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P],
-    "mmdfn_linear_planes_group_in": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _F, _P],
-    "mmdfn_linear_planes_group_party": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _F,
-                                        _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "mmdfn_linear_group_supported": [_I, _I, _I],
-    "mmdfn_linear_group": [_I] + [_P] * 15 + [_I, _P],
-    "mmdfn_linear_group_addend": [_I] + [_P] * 17 + [_I, _P],
-    "mmdfn_linear_group_seg2": [_I] + [_P] * 22 + [_I, _P],
-    "mmdfn_softmax_scale_fwd": [_P, _P, _P, _P, _I, _I, _P],
-    "mmdfn_softmax_scale_bwd": [_P, _P, _P, _P, _P, _I, _I, _P],
-    "mmdfn_mfn_mem_fwd": [_P] * 6 + [_L, _P],
-    "mmdfn_mfn_mem_bwd": [_P] * 7 + [_L, _P],
-    "mmdfn_gated_pair_fwd": [_P] * 8 + [_I, _I, _I, _P],
-    "mmdfn_gated_pair_bwd": [_P] * 12 + [_I, _I, _I, _P],
-    "mmdfn_rowscale_colsum": [_P, _P, _P, _P, _I, _I, _P],
-    "mmdfn_gemm_tn_splits": [_I, _I, _I],
-    "mmdfn_gemm_tn": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "mmdfn_gemm_tn_grouped_workspace": [_I, _P, _P, _P],
-    "mmdfn_gemm_tn_grouped": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_gemm_tn_batch_workspace": [_I, _P, _P, _I, _P, _P],
-    "mmdfn_gemm_tn_batch": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_wgrad_riders_stage": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_wgrad_riders_staged": [_P],
-    "mmdfn_wgrad_riders_flush": [_P, _P],
-    "mmdfn_wgrad_riders_drain": [_P, _P, _I],
-    "mmdfn_gru_seq_bwd_idle_cus": [_I, _P],
-    "mmdfn_gru_seq_bwd_step_ns": [_I, _P],
-    "mmdfn_gemm_tn_batch_ext": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                                _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mmdfn_head_bwd_groups": [],
-    "mmdfn_head_bwd_partial": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P],
-    "mmdfn_colsum_partial": [_P, _L, _I, _I, _P, _P],
-    "mmdfn_head_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _P],
-    "mmdfn_head_bwd_workspace": [_I, _I],
-    "mmdfn_head_bwd": [_P] * 9 + [_L, _I, _I, _I, _I, _I, _F, _P],
-    "mmdfn_head_fwd_act": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _F, _I, _P],
-    "mmdfn_head_bwd_act": [_P] * 9 + [_L, _I, _I, _I, _I, _I, _F, _I, _P],
-    "mmdfn_head_bwd_partial_act": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
-    "mmdfn_lmf_bwd_width": [_I, _I],
-    "mmdfn_lmf_fwd": [_P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _L, _I, _I, _I, _I, _P],
-    "mmdfn_lmf_bwd": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
-    "mmdfn_tfn_workspace": [_L, _I, _I, _I, _I, _I],
-    "mmdfn_tfn_fwd": [_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _L, _F, _F, _P, _P, _L, _I, _I, _I, _I, _I, _P],
-    "mmdfn_tfn_bwd_input": [_P, _P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
-    "mmdfn_tfn_bwd_weight": [_P, _P, _P, _P, _I, _I, _I, _P, _F, _F, _P, _L, _I, _I, _I, _I, _P],
-    "mmdfn_tfn_keep_flags": [_P, _F, _P, _L, _L, _L, _L, _P],
-    "mmdfn_focal_loss_fwd": [_P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
-    "mmdfn_focal_loss_bwd": [_P, _P, _P, _P, _L, _I, _P],
-    "mmdfn_focal_loss_fwd_grad": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
-    "mmdfn_focal_loss_fwd_ignore": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _L, _P],
-    "mmdfn_focal_loss_bwd_ignore": [_P, _P, _P, _P, _P, _L, _I, _L, _P],
-    "mmdfn_adam_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P],
-    "mmdfn_adam_state_bytes": [],
-    "mmdfn_grad_sumsq": [_P, _L, _P, _I, _P, _P],
-    "mmdfn_adam_prepare": [_P, _P, _I, _F, _F, _P],
-    "mmdfn_adam_step_state": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _P],
-    "mmdfn_party_gather": [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "mmdfn_party_gather_bwd": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "mmdfn_party_gather_bwd_colsum": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "mmdfn_party_combine": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "mmdfn_party_combine_bwd": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "mmdfn_party_combine_bwd_dst": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "mmdfn_mask_scale": [_I, _P, _P, _P, _P, _F, _P],
-    "mmdfn_keep_flags": [_P, _L, _F, _P, _P],
-    "mmdfn_keep_flags_stage": [_P, _L, _F, _P, _P, _P],
-    "mmdfn_keep_flags_flush": [_P, _P],
-    "mmdfn_gru_seq_fwd_takes_flags": [_I, _P],
-    "mmdfn_colsum_workspace": [_I],
-    "mmdfn_colsum": [_P, _L, _I, _I, _P, _P, _P],
-}
+
+class HipLibraryError(RuntimeError):
+    pass
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
+
+
+def _ctype(text, decl):
+    """ctypes type of one parameter or return type as the header spells it: anything with ``*`` is a pointer."""
+    if "*" in text:
+        return ctypes.c_void_p
+    text = text.strip()
+    words = [w for w in text.split() if w != "const"]
+    if "[" in text or not words:
+        raise HipLibraryError("cannot split the declaration '%s' of include/mmdfn_hip.h" % decl)
+    if words[0] == "struct" or words[0].startswith("mmdfn_"):
+        raise HipLibraryError("'%s' is passed by value in '%s': the binding takes structs by pointer only" % (text, decl))
+    if words[0] not in _SCALARS or len(words) > 2:      # [type] or [type, name]
+        raise HipLibraryError("unknown scalar type '%s' in '%s'" % (text, decl))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """(argtypes, restypes) by symbol name for every ``mmdfn_*(...)`` declaration of the C header ``text``.  Strict: a
+    declaration it cannot read raises HipLibraryError; no type is ever guessed."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    argtypes, restypes = {}, {}
+    for stmt in re.split(r"[;{}]", text):
+        if not re.search(r"\bmmdfn_\w+\s*\(", stmt):
+            continue
+        decl = " ".join(stmt.split())
+        m = re.fullmatch(r"(\w[\w\s*]*?)\s*\b(mmdfn_\w+)\s*\(([^()]*)\)", decl)
+        if m is None:
+            raise HipLibraryError("cannot split the declaration '%s' of include/mmdfn_hip.h" % decl)
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        restypes[name] = _ctype(ret, decl)
+        argtypes[name] = [_ctype(p, decl) for p in params]
+    return argtypes, restypes
+
+
+# name -> argtypes / return type, read from the header that build._digest() already stamps the library with
+with open(os.path.join(_build.INCLUDE, "mmdfn_hip.h")) as _f:
+    SIGNATURES, RESTYPES = parse_header(_f.read())
 
 ABI_VERSION = 23
 
@@ -138,10 +74,6 @@ class AdamState(ctypes.Structure):
 def adam_state_word(name):
     """Index of field ``name`` in the block viewed as 16 four-byte words."""
     return getattr(AdamState, name).offset // 4
-
-
-class HipLibraryError(RuntimeError):
-    pass
 
 
 _libs = {}
@@ -180,7 +112,7 @@ def lib():
         except AttributeError as e:
             raise HipLibraryError("%s lacks symbol %s (stale build?)" % (os.path.basename(path), name)) from e
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name.endswith(("_workspace", "_bytes")) else ctypes.c_int
+        fn.restype = RESTYPES[name]
     if handle.mmdfn_abi_version() != ABI_VERSION:
         raise HipLibraryError("%s ABI version mismatch" % os.path.basename(path))
     _libs[tuning] = handle
@@ -190,7 +122,7 @@ def lib():
 def riders_context():
     """An empty rider context (include/mmdfn_hip.h mmdfn_riders_bytes): zeroed host memory that the rider entry points stage
     work in and the GRU launches given it take work from."""
-    return ctypes.create_string_buffer(int(lib().mmdfn_riders_bytes()))
+    return ctypes.create_string_buffer(int(query("mmdfn_riders_bytes")))
 
 
 def ptr(t):
@@ -206,6 +138,33 @@ def stream():
 def check(rc, what):
     if rc != 0:
         raise HipLibraryError("%s failed with code %d" % (what, rc))
+
+
+def _miscall(name, nargs):
+    if name not in SIGNATURES:
+        return HipLibraryError("%s is not declared in include/mmdfn_hip.h" % name)
+    return HipLibraryError("%s takes %d arguments, got %d" % (name, len(SIGNATURES[name]), nargs))
+
+
+def query(name, *args):
+    """Value of entry point ``name`` (a size or a predicate: *_workspace, *_bytes, *_supported, ...).  ctypes takes surplus
+    arguments in silence, so the count is checked against the header before the library is entered."""
+    argtypes = SIGNATURES.get(name)
+    if argtypes is None or len(args) != len(argtypes):
+        raise _miscall(name, len(args))
+    return getattr(_libs.get(_tuning) or lib(), name)(*args)
+
+
+def call(name, *args, allow=()):
+    """Run entry point ``name`` after the same count check; raises unless it returns 0 or a code in ``allow``.  Returns the
+    code.  (Not written through ``query``: a Python frame per launch is what the eager step is made of.)"""
+    argtypes = SIGNATURES.get(name)
+    if argtypes is None or len(args) != len(argtypes):
+        raise _miscall(name, len(args))
+    rc = getattr(_libs.get(_tuning) or lib(), name)(*args)
+    if rc != 0 and rc not in allow:
+        raise HipLibraryError("%s failed with code %d" % (name, rc))
+    return rc
 
 
 def require_cuda(*tensors):

@@ -41,7 +41,6 @@ class _GcnStack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, tiles, cross, masks, mscale, lay, symmetric, lamda, alpha, reason, use_residue, W0, b0, w_ih, w_hh,
                 b_ih, b_hh, *convW):
-        lib = _hip.lib()
         P, st = _hip.ptr, _hip.stream()
         x = x.contiguous()
         R, F = x.shape
@@ -59,8 +58,7 @@ class _GcnStack(torch.autograd.Function):
         xd = out if use_residue else new(R, F)                 # x_d lives in the left F columns of the residue output
         ldxd = F + H if use_residue else F
         h0, cur = new(R, H), new(R, H)
-        _hip.check(lib.mmdfn_gcn_input_fwd(P(x), P(mx), P(W0), P(b0), P(m0), P(xd), P(h0), P(cur), R, F, H, ldxd, mscale, st),
-                   "mmdfn_gcn_input_fwd")
+        _hip.call("mmdfn_gcn_input_fwd", P(x), P(mx), P(W0), P(b0), P(m0), P(xd), P(h0), P(cur), R, F, H, ldxd, mscale, st)
         h = c = None
         layers = []
         # the layers' hidden states are column blocks of ONE (R, nl H) buffer: what every layer propagates (zin_l) is then the
@@ -68,17 +66,17 @@ class _GcnStack(torch.autograd.Function):
         # the layers, model_GCN.py:461-472), instead of nl read-modify-write passes over the tile array
         zin_all = new(R, nl * H) if reason else None
         planes = None
-        if PRECUT and reason and nl > 1 and lib.mmdfn_lstm_gate_takes_planes(R, H):
+        if PRECUT and reason and nl > 1 and _hip.query("mmdfn_lstm_gate_takes_planes", R, H):
             # many-row launches (bf16-piece form): the cell's weights are cut ONCE for all layers of this forward pass
-            planes = new(int(lib.mmdfn_lstm_gate_planes_workspace(H)))
-            _hip.check(lib.mmdfn_lstm_gate_cut_weights(P(w_ih), P(w_hh), P(planes), H, st), "mmdfn_lstm_gate_cut_weights")
+            planes = new(int(_hip.query("mmdfn_lstm_gate_planes_workspace", H)))
+            _hip.call("mmdfn_lstm_gate_cut_weights", P(w_ih), P(w_hh), P(planes), H, st)
         for i in range(nl):
             q = cur
             rec = dict(q=q, h_prev=h, c_prev=c)
             if reason:
                 gates, h_new, c_new = new(R, 4 * H), zin_all[:, i * H:(i + 1) * H], new(R, H)
-                _hip.check(lib.mmdfn_lstm_gate_fwd_pre(P(q), P(h), P(c), P(w_ih), P(w_hh), P(b_ih), P(b_hh), P(gates), P(h_new),
-                                                       P(c_new), R, H, nl * H, P(planes), st), "mmdfn_lstm_gate_fwd_pre")
+                _hip.call("mmdfn_lstm_gate_fwd_pre", P(q), P(h), P(c), P(w_ih), P(w_hh), P(b_ih), P(b_hh), P(gates), P(h_new),
+                          P(c_new), R, H, nl * H, P(planes), st)
                 rec.update(gates=gates, c_new=c_new)
                 h, c = h_new, c_new
                 zin = h_new
@@ -96,15 +94,13 @@ class _GcnStack(torch.autograd.Function):
             # short dialogues: propagate + layer update of a strip of rows in ONE launch (csrc/gcn_small.hip; hi is still written
             # out for the backward pass); -2 = shape not covered: the two launches
             hi = new(R, H)
-            rc = lib.mmdfn_prop_layer_fwd(P(tiles), P(cross), P(zin), zin.stride(0), *_lay_args(lay), lay.B, lay.M, lay.N,
-                                          lay.max_len, P(h0), P(convW[i]), P(q if reason else None), P(ml[i]), P(hi), P(dst),
-                                          P(gmask), theta, alpha, H, ldo, mscale, st) if FUSE_PROP_LAYER else -2
+            rc = _hip.call("mmdfn_prop_layer_fwd", P(tiles), P(cross), P(zin), zin.stride(0), *_lay_args(lay), lay.B, lay.M, lay.N,
+                           lay.max_len, P(h0), P(convW[i]), P(q if reason else None), P(ml[i]), P(hi), P(dst),
+                           P(gmask), theta, alpha, H, ldo, mscale, st, allow=(-2,)) if FUSE_PROP_LAYER else -2
             if rc == -2:
                 hi = ops.propagate_raw(tiles, cross, zin, lay, out=hi)
-                _hip.check(lib.mmdfn_gcnii_layer_fwd(P(hi), P(h0), P(convW[i]), P(q if reason else None), P(ml[i]), P(dst),
-                                                     P(gmask), theta, alpha, R, H, ldo, mscale, st), "mmdfn_gcnii_layer_fwd")
-            else:
-                _hip.check(rc, "mmdfn_prop_layer_fwd")
+                _hip.call("mmdfn_gcnii_layer_fwd", P(hi), P(h0), P(convW[i]), P(q if reason else None), P(ml[i]), P(dst),
+                          P(gmask), theta, alpha, R, H, ldo, mscale, st)
             rec.update(zin=zin, hi=hi, gmask=gmask, theta=theta)
             layers.append(rec)
             cur = dst
@@ -119,7 +115,6 @@ class _GcnStack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _hip.lib()
         P, st = _hip.ptr, _hip.stream()
         m = ctx.misc
         R, F, H = m["R"], m["F"], m["H"]
@@ -166,8 +161,8 @@ class _GcnStack(torch.autograd.Function):
             L = ctx.layers[i]
             dP = new(R, H)
             dhi = dhi_all[:, i * H:(i + 1) * H] if one_outer else new(R, H)
-            _hip.check(lib.mmdfn_gcnii_layer_bwd_ld(P(dcur), P(L["gmask"]), P(convW[i]), P(dP), P(dhi), P(dh0), L["theta"],
-                                                    m["alpha"], R, H, lddo, acc_h0, dhi.stride(0), st), "mmdfn_gcnii_layer_bwd_ld")
+            _hip.call("mmdfn_gcnii_layer_bwd_ld", P(dcur), P(L["gmask"]), P(convW[i]), P(dP), P(dhi), P(dh0), L["theta"],
+                      m["alpha"], R, H, lddo, acc_h0, dhi.stride(0), st)
             acc_h0 = 1
             # dW_i = [hi | h0]^T dP: two row ranges of the (2H, H) parameter, the concatenated operand never exists
             wgrad(L["hi"], dP, convW[i], rows=(0, H))
@@ -180,9 +175,9 @@ class _GcnStack(torch.autograd.Function):
                 dG, dq = new(R, 4 * H), new(R, H)
                 dh_prev = new(R, H) if has_h else None
                 dc_prev = new(R, H) if has_h else None
-                _hip.check(lib.mmdfn_lstm_gate_bwd(P(L["gates"]), P(L["c_prev"]), P(L["c_new"]), P(dz), P(dh_carry),
-                                                   P(dc_carry), P(w_ih), P(w_hh), P(dcur), P(dG), P(dc_prev), P(dq),
-                                                   P(dh_prev), R, H, 1 if has_h else 0, lddo, st), "mmdfn_lstm_gate_bwd")
+                _hip.call("mmdfn_lstm_gate_bwd", P(L["gates"]), P(L["c_prev"]), P(L["c_new"]), P(dz), P(dh_carry),
+                          P(dc_carry), P(w_ih), P(w_hh), P(dcur), P(dG), P(dc_prev), P(dq),
+                          P(dh_prev), R, H, 1 if has_h else 0, lddo, st)
                 wgrad(dG, L["q"], w_ih, [b_ih, b_hh])
                 if has_h:
                     wgrad(dG, L["h_prev"], w_hh)
@@ -194,8 +189,8 @@ class _GcnStack(torch.autograd.Function):
             # dA = [dhi_1 | .. | dhi_nl] [zin_1 | .. | zin_nl]^T on the tile / diagonal pattern: the tile array is written once
             dtiles, dcross = ops.tile_outer_raw(dhi_all, m["zin_all"], lay)
         dpre, dx = new(R, H), new(R, F)
-        _hip.check(lib.mmdfn_gcn_input_bwd(P(dcur), P(m["m0"]), P(dh0), P(m["h0"]), P(W0), P(dxd), P(m["mx"]), P(dpre), P(dx), R,
-                                           F, H, lddxd, m["mscale"], st), "mmdfn_gcn_input_bwd")
+        _hip.call("mmdfn_gcn_input_bwd", P(dcur), P(m["m0"]), P(dh0), P(m["h0"]), P(W0), P(dxd), P(m["mx"]), P(dpre), P(dx), R,
+                  F, H, lddxd, m["mscale"], st)
         xd = m["xd"][:, :F] if m["use_residue"] else m["xd"]
         wgrad(dpre, xd, W0, [b0] if b0 is not None else [])
         pg = [None if p is None else inline.get(id(p)) for p in (W0, b0, w_ih, w_hh, b_ih, b_hh)]

@@ -89,13 +89,12 @@ class _GruRecurrence(torch.autograd.Function):
                 riders = _hip.riders_context()
                 ops.stage_flag_draw(flag_p, gis[0].device, rows, riders)
             try:
-                rc = _hip.lib().mmdfn_gru_seq_fwd(n, _hip.ptr_array(gis), _hip.ptr_array(whh), _hip.ptr_array(bhh),
-                                                  _hip.ptr_array(ys), _hip.ptr_array(gates), _hip.int_array(rows),
-                                                  _hip.int_array(Ts), H, riders, _hip.stream())
+                _hip.call("mmdfn_gru_seq_fwd", n, _hip.ptr_array(gis), _hip.ptr_array(whh), _hip.ptr_array(bhh),
+                          _hip.ptr_array(ys), _hip.ptr_array(gates), _hip.int_array(rows),
+                          _hip.int_array(Ts), H, riders, _hip.stream())
             finally:
                 if riders is not None:
                     ops.finish_flag_draw(riders)
-            _hip.check(rc, "mmdfn_gru_seq_fwd")
         else:
             if ytab is not None:
                 ytab = ytab.contiguous()
@@ -104,10 +103,9 @@ class _GruRecurrence(torch.autograd.Function):
                     raise ValueError("ytab must be (T, 1, 2H)")
             ytabs = [ytab if g == seg.group else None for g in range(n)]
             rk, P, BP, tdir = seg.arrays(n)
-            rc = _hip.lib().mmdfn_gru_seq_fwd_seg(n, _hip.ptr_array(gis), _hip.ptr_array(whh), _hip.ptr_array(bhh),
-                                                  _hip.ptr_array(ys), _hip.ptr_array(gates), _hip.int_array(rows),
-                                                  _hip.int_array(Ts), H, rk, P, BP, tdir, _hip.ptr_array(ytabs), _hip.stream())
-            _hip.check(rc, "mmdfn_gru_seq_fwd_seg")
+            _hip.call("mmdfn_gru_seq_fwd_seg", n, _hip.ptr_array(gis), _hip.ptr_array(whh), _hip.ptr_array(bhh),
+                      _hip.ptr_array(ys), _hip.ptr_array(gates), _hip.int_array(rows),
+                      _hip.int_array(Ts), H, rk, P, BP, tdir, _hip.ptr_array(ytabs), _hip.stream())
         ctx.n = n
         ctx.seg = seg
         ctx.has_tab = ytab is not None
@@ -131,12 +129,11 @@ class _GruRecurrence(torch.autograd.Function):
             # weight gradients queued so far ride on the CUs this recurrence leaves idle (ops_wgrad.stage_riders)
             riders = ops.stage_riders(rows, Ts)
             try:
-                rc = _hip.lib().mmdfn_gru_seq_bwd(n, _hip.ptr_array(dys), _hip.ptr_array(ys), _hip.ptr_array(gates),
-                                                  _hip.ptr_array(whh), _hip.ptr_array(dgi), _hip.ptr_array(dgh),
-                                                  _hip.int_array(rows), _hip.int_array(Ts), H, riders, _hip.stream())
+                _hip.call("mmdfn_gru_seq_bwd", n, _hip.ptr_array(dys), _hip.ptr_array(ys), _hip.ptr_array(gates),
+                          _hip.ptr_array(whh), _hip.ptr_array(dgi), _hip.ptr_array(dgh),
+                          _hip.int_array(rows), _hip.int_array(Ts), H, riders, _hip.stream())
             finally:
                 ops.finish_riders()
-            _hip.check(rc, "mmdfn_gru_seq_bwd")
         else:
             g0 = seg.group
             dhinit = kout = None
@@ -144,18 +141,16 @@ class _GruRecurrence(torch.autograd.Function):
                 dhinit = torch.empty(rows[g0], H, dtype=torch.float32, device=ys[g0].device)
                 kout = torch.empty(rows[g0], dtype=torch.int32, device=ys[g0].device)
             rk, P, BP, tdir = seg.arrays(n)
-            rc = _hip.lib().mmdfn_gru_seq_bwd_seg(n, _hip.ptr_array(dys), _hip.ptr_array(ys), _hip.ptr_array(gates),
-                                                  _hip.ptr_array(whh), _hip.ptr_array(dgi), _hip.ptr_array(dgh),
-                                                  _hip.int_array(rows), _hip.int_array(Ts), H, rk, P, BP, tdir,
-                                                  _hip.ptr_array([dhinit if g == g0 else None for g in range(n)]),
-                                                  _hip.ptr_array([kout if g == g0 else None for g in range(n)]), _hip.stream())
-            _hip.check(rc, "mmdfn_gru_seq_bwd_seg")
+            _hip.call("mmdfn_gru_seq_bwd_seg", n, _hip.ptr_array(dys), _hip.ptr_array(ys), _hip.ptr_array(gates),
+                      _hip.ptr_array(whh), _hip.ptr_array(dgi), _hip.ptr_array(dgh),
+                      _hip.int_array(rows), _hip.int_array(Ts), H, rk, P, BP, tdir,
+                      _hip.ptr_array([dhinit if g == g0 else None for g in range(n)]),
+                      _hip.ptr_array([kout if g == g0 else None for g in range(n)]), _hip.stream())
             if ctx.has_tab and ctx.needs_input_grad[1]:
                 # what reaches the all-padding sequence from the rows truncated against it (its own backward follows)
                 dyt = torch.empty(Ts[g0], 1, 2 * H, dtype=torch.float32, device=ys[g0].device)
-                rc = _hip.lib().mmdfn_gru_tab_reduce(_hip.ptr(dys[g0]), _hip.ptr(kout), _hip.ptr(dhinit), _hip.ptr(dyt),
-                                                     rows[g0], Ts[g0], H, seg.tdir, _hip.stream())
-                _hip.check(rc, "mmdfn_gru_tab_reduce")
+                _hip.call("mmdfn_gru_tab_reduce", _hip.ptr(dys[g0]), _hip.ptr(kout), _hip.ptr(dhinit), _hip.ptr(dyt),
+                          rows[g0], Ts[g0], H, seg.tdir, _hip.stream())
         # recurrent-weight gradients of every group and direction join the step's weight-gradient batch:
         #   dW_hh = sum_t dgh_t (x) h_{t-1}   forward: h_{t-1} = y[t-1] (row shift -R), reverse: y[t+1] (+R)
         #   db_hh = sum_t dgh_t                = the column sums of the same operand
@@ -234,10 +229,9 @@ class _GruTable(torch.autograd.Function):
         bhh = [bf.detach().contiguous(), br.detach().contiguous()]
         y = torch.empty(T, 1, 2 * H, dtype=torch.float32, device=gi.device)
         gates = torch.empty(T, 1, 2, 4, H, dtype=torch.float32, device=gi.device)
-        rc = _hip.lib().mmdfn_gru_seq_fwd(1, _hip.ptr_array([gi]), _hip.ptr_array(whh), _hip.ptr_array(bhh),
-                                          _hip.ptr_array([y]), _hip.ptr_array([gates]), _hip.int_array([1]),
-                                          _hip.int_array([T]), H, None, _hip.stream())
-        _hip.check(rc, "mmdfn_gru_seq_fwd")
+        _hip.call("mmdfn_gru_seq_fwd", 1, _hip.ptr_array([gi]), _hip.ptr_array(whh), _hip.ptr_array(bhh),
+                  _hip.ptr_array([y]), _hip.ptr_array([gates]), _hip.int_array([1]),
+                  _hip.int_array([T]), H, None, _hip.stream())
         ctx.T = T
         ctx.params = params            # (b_ih_rev, w_hh_rev, b_hh_rev): the parameter objects themselves
         ctx.save_for_backward(y, gates, *whh)
@@ -250,10 +244,9 @@ class _GruTable(torch.autograd.Function):
         dy = dy.contiguous()
         dgi = torch.empty(T, 1, 6 * H, dtype=torch.float32, device=y.device)
         dgh = torch.empty_like(dgi)
-        rc = _hip.lib().mmdfn_gru_seq_bwd(1, _hip.ptr_array([dy]), _hip.ptr_array([y]), _hip.ptr_array([gates]),
-                                          _hip.ptr_array([wf, wr]), _hip.ptr_array([dgi]), _hip.ptr_array([dgh]),
-                                          _hip.int_array([1]), _hip.int_array([T]), H, None, _hip.stream())
-        _hip.check(rc, "mmdfn_gru_seq_bwd")
+        _hip.call("mmdfn_gru_seq_bwd", 1, _hip.ptr_array([dy]), _hip.ptr_array([y]), _hip.ptr_array([gates]),
+                  _hip.ptr_array([wf, wr]), _hip.ptr_array([dgi]), _hip.ptr_array([dgh]),
+                  _hip.int_array([1]), _hip.int_array([T]), H, None, _hip.stream())
         bir, w, b = ctx.params
         d2, g2, y2 = dgh.view(T, 6 * H)[:, 3 * H:], dgi.view(T, 6 * H)[:, 3 * H:], y.view(T, 2 * H)[:, H:]
         dw = torch.empty(3 * H, H, dtype=torch.float32, device=y.device)

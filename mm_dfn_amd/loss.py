@@ -30,10 +30,9 @@ class _FocalLossHip(torch.autograd.Function):
         coef = torch.empty(N, dtype=torch.float32, device=logp.device)
         want = ctx.needs_input_grad[0]
         dunit = torch.empty(N, C, dtype=torch.float32, device=logp.device) if want else None
-        rc = _hip.lib().mmdfn_focal_loss_fwd_grad(_hip.ptr(logp), _hip.ptr(target), _hip.ptr(alpha), _hip.ptr(loss),
-                                                  _hip.ptr(coef), _hip.ptr(dunit), N, C, float(gamma),
-                                                  1 if size_average else 0, _hip.stream())
-        _hip.check(rc, "mmdfn_focal_loss_fwd_grad")
+        _hip.call("mmdfn_focal_loss_fwd_grad", _hip.ptr(logp), _hip.ptr(target), _hip.ptr(alpha), _hip.ptr(loss),
+                  _hip.ptr(coef), _hip.ptr(dunit), N, C, float(gamma),
+                  1 if size_average else 0, _hip.stream())
         ctx.save_for_backward(coef, target)
         ctx.dunit = dunit
         ctx.C = C
@@ -51,9 +50,8 @@ class _FocalLossHip(torch.autograd.Function):
         N = coef.shape[0]
         dlogp = torch.empty(N, ctx.C, dtype=torch.float32, device=coef.device)
         dl = dloss.contiguous().to(torch.float32)
-        rc = _hip.lib().mmdfn_focal_loss_bwd(_hip.ptr(coef), _hip.ptr(target), _hip.ptr(dl), _hip.ptr(dlogp), N, ctx.C,
-                                             _hip.stream())
-        _hip.check(rc, "mmdfn_focal_loss_bwd")
+        _hip.call("mmdfn_focal_loss_bwd", _hip.ptr(coef), _hip.ptr(target), _hip.ptr(dl), _hip.ptr(dlogp), N, ctx.C,
+                  _hip.stream())
         return dlogp, None, None, None, None
 
 
@@ -70,10 +68,9 @@ class _FocalLossIgnoreHip(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=logp.device)
         scale = torch.empty(1, dtype=torch.float32, device=logp.device)
         coef = torch.empty(N, dtype=torch.float32, device=logp.device)
-        rc = _hip.lib().mmdfn_focal_loss_fwd_ignore(_hip.ptr(logp), _hip.ptr(target), _hip.ptr(alpha), _hip.ptr(loss),
-                                                    _hip.ptr(coef), _hip.ptr(scale), N, C, float(gamma),
-                                                    1 if size_average else 0, int(ignore_index), _hip.stream())
-        _hip.check(rc, "mmdfn_focal_loss_fwd_ignore")
+        _hip.call("mmdfn_focal_loss_fwd_ignore", _hip.ptr(logp), _hip.ptr(target), _hip.ptr(alpha), _hip.ptr(loss),
+                  _hip.ptr(coef), _hip.ptr(scale), N, C, float(gamma),
+                  1 if size_average else 0, int(ignore_index), _hip.stream())
         ctx.save_for_backward(coef, target, scale)
         ctx.C, ctx.ignore = C, int(ignore_index)
         return loss
@@ -85,9 +82,8 @@ class _FocalLossIgnoreHip(torch.autograd.Function):
         N = coef.shape[0]
         dlogp = torch.empty(N, ctx.C, dtype=torch.float32, device=coef.device)
         dl = dloss.contiguous().to(torch.float32)
-        rc = _hip.lib().mmdfn_focal_loss_bwd_ignore(_hip.ptr(coef), _hip.ptr(target), _hip.ptr(dl), _hip.ptr(scale),
-                                                    _hip.ptr(dlogp), N, ctx.C, ctx.ignore, _hip.stream())
-        _hip.check(rc, "mmdfn_focal_loss_bwd_ignore")
+        _hip.call("mmdfn_focal_loss_bwd_ignore", _hip.ptr(coef), _hip.ptr(target), _hip.ptr(dl), _hip.ptr(scale),
+                  _hip.ptr(dlogp), N, ctx.C, ctx.ignore, _hip.stream())
         return dlogp, None, None, None, None, None
 
 

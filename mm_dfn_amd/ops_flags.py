@@ -126,7 +126,7 @@ def stage_flag_draw(p, device, rows, riders):
     if k in scope.bufs:
         return
     want = _FLAG_HINT.get((scope.key,) + k, 0)
-    if want <= 0 or not _hip.lib().mmdfn_gru_seq_fwd_takes_flags(len(rows), _hip.int_array(rows)):
+    if want <= 0 or not _hip.query("mmdfn_gru_seq_fwd_takes_flags", len(rows), _hip.int_array(rows)):
         return
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if _FLAG_STATE.get(idx) is None:
@@ -136,7 +136,7 @@ def stage_flag_draw(p, device, rows, riders):
 
 def finish_flag_draw(riders):
     """Behind that launch: a draw staged in ``riders`` that the launch did not take (another kernel form) is launched now."""
-    _hip.check(_hip.lib().mmdfn_keep_flags_flush(riders, _hip.stream()), "mmdfn_keep_flags_flush")
+    _hip.call("mmdfn_keep_flags_flush", riders, _hip.stream())
 
 
 def draw_flags(n, p, device, riders=None):
@@ -166,12 +166,10 @@ def draw_flags(n, p, device, riders=None):
         ent[1] = (now[0], int(gen.get_offset()))
     _FLAG_CONSUMED[idx] = _FLAG_CONSUMED.get(idx, 0) + 4 * ((n8 + 3) // 4)
     out = torch.empty(n, dtype=torch.float32, device=device)
-    lib = _hip.lib()
     if riders is None:
-        rc = lib.mmdfn_keep_flags(_hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), _hip.stream())
+        _hip.call("mmdfn_keep_flags", _hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), _hip.stream())
     else:
-        rc = lib.mmdfn_keep_flags_stage(_hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), riders, _hip.stream())
-    _hip.check(rc, "mmdfn_keep_flags")
+        _hip.call("mmdfn_keep_flags_stage", _hip.ptr(out), n, float(1.0 - p), _hip.ptr(ent[0]), riders, _hip.stream())
     return out
 
 
@@ -248,9 +246,8 @@ class _MaskScale(torch.autograd.Function):
         for x, m in zip(xs, masks):
             if m.numel() != x.numel() or x.numel() % 4 or x.data_ptr() % 16 or m.data_ptr() % 16:
                 raise _hip.HipLibraryError("mask_scale: flags must match the tensor (multiple of 4 elements, 16-byte aligned)")
-        rc = _hip.lib().mmdfn_mask_scale(len(xs), _hip.ptr_array(xs), _hip.ptr_array(masks), _hip.ptr_array(outs),
-                                         _hip.long_array([x.numel() for x in xs]), scale, _hip.stream())
-        _hip.check(rc, "mmdfn_mask_scale")
+        _hip.call("mmdfn_mask_scale", len(xs), _hip.ptr_array(xs), _hip.ptr_array(masks), _hip.ptr_array(outs),
+                  _hip.long_array([x.numel() for x in xs]), scale, _hip.stream())
 
     @staticmethod
     def backward(ctx, *douts):

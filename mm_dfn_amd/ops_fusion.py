@@ -35,8 +35,8 @@ class _SoftmaxScale(torch.autograd.Function):
         _hip.require_cuda(z, c)
         z, c = z.contiguous(), c.contiguous()
         att, out = torch.empty_like(z), torch.empty_like(z)
-        _hip.check(_hip.lib().mmdfn_softmax_scale_fwd(_hip.ptr(z), _hip.ptr(c), _hip.ptr(att), _hip.ptr(out), z.shape[0],
-                                                      z.shape[1], _hip.stream()), "mmdfn_softmax_scale_fwd")
+        _hip.call("mmdfn_softmax_scale_fwd", _hip.ptr(z), _hip.ptr(c), _hip.ptr(att), _hip.ptr(out), z.shape[0],
+                  z.shape[1], _hip.stream())
         ctx.save_for_backward(att, c)
         return out
 
@@ -45,8 +45,8 @@ class _SoftmaxScale(torch.autograd.Function):
         att, c = ctx.saved_tensors
         dout = dout.contiguous()
         dz, dc = torch.empty_like(att), torch.empty_like(att)
-        _hip.check(_hip.lib().mmdfn_softmax_scale_bwd(_hip.ptr(att), _hip.ptr(c), _hip.ptr(dout), _hip.ptr(dz), _hip.ptr(dc),
-                                                      att.shape[0], att.shape[1], _hip.stream()), "mmdfn_softmax_scale_bwd")
+        _hip.call("mmdfn_softmax_scale_bwd", _hip.ptr(att), _hip.ptr(c), _hip.ptr(dout), _hip.ptr(dz), _hip.ptr(dc),
+                  att.shape[0], att.shape[1], _hip.stream())
         return dz, dc
 
 
@@ -63,8 +63,8 @@ class _MfnMem(torch.autograd.Function):
         u, v1, v2, mem = u.contiguous(), v1.contiguous(), v2.contiguous(), mem.contiguous()
         out = torch.empty_like(mem)
         saved = torch.empty(3, mem.numel(), dtype=mem.dtype, device=mem.device)
-        _hip.check(_hip.lib().mmdfn_mfn_mem_fwd(_hip.ptr(u), _hip.ptr(v1), _hip.ptr(v2), _hip.ptr(mem), _hip.ptr(out),
-                                                _hip.ptr(saved), mem.numel(), _hip.stream()), "mmdfn_mfn_mem_fwd")
+        _hip.call("mmdfn_mfn_mem_fwd", _hip.ptr(u), _hip.ptr(v1), _hip.ptr(v2), _hip.ptr(mem), _hip.ptr(out),
+                  _hip.ptr(saved), mem.numel(), _hip.stream())
         ctx.save_for_backward(saved, mem)
         return out
 
@@ -73,8 +73,8 @@ class _MfnMem(torch.autograd.Function):
         saved, mem = ctx.saved_tensors
         dout = dout.contiguous()
         du, dv1, dv2, dmem = (torch.empty_like(mem) for _ in range(4))
-        _hip.check(_hip.lib().mmdfn_mfn_mem_bwd(_hip.ptr(saved), _hip.ptr(mem), _hip.ptr(dout), _hip.ptr(du), _hip.ptr(dv1),
-                                                _hip.ptr(dv2), _hip.ptr(dmem), mem.numel(), _hip.stream()), "mmdfn_mfn_mem_bwd")
+        _hip.call("mmdfn_mfn_mem_bwd", _hip.ptr(saved), _hip.ptr(mem), _hip.ptr(dout), _hip.ptr(du), _hip.ptr(dv1),
+                  _hip.ptr(dv2), _hip.ptr(dmem), mem.numel(), _hip.stream())
         return du, dv1, dv2, dmem
 
 
@@ -93,8 +93,8 @@ class _GatedPair(torch.autograd.Function):
         C = pm.shape[1]
         out = torch.empty_like(pm)
         zs = torch.empty(R, dtype=xm.dtype, device=xm.device)
-        _hip.check(_hip.lib().mmdfn_gated_pair_fwd(_hip.ptr(xm), _hip.ptr(xn), _hip.ptr(w), _hip.ptr(b), _hip.ptr(pm), _hip.ptr(pn),
-                                                   _hip.ptr(out), _hip.ptr(zs), R, D, C, _hip.stream()), "mmdfn_gated_pair_fwd")
+        _hip.call("mmdfn_gated_pair_fwd", _hip.ptr(xm), _hip.ptr(xn), _hip.ptr(w), _hip.ptr(b), _hip.ptr(pm), _hip.ptr(pn),
+                  _hip.ptr(out), _hip.ptr(zs), R, D, C, _hip.stream())
         ctx.save_for_backward(xm, xn, pm, pn, w, zs)
         return out
 
@@ -106,13 +106,11 @@ class _GatedPair(torch.autograd.Function):
         C = pm.shape[1]
         dxm, dxn, dpm, dpn = torch.empty_like(xm), torch.empty_like(xn), torch.empty_like(pm), torch.empty_like(pn)
         dpre = torch.empty(R, dtype=xm.dtype, device=xm.device)
-        lib = _hip.lib()
-        _hip.check(lib.mmdfn_gated_pair_bwd(_hip.ptr(xm), _hip.ptr(xn), _hip.ptr(w), _hip.ptr(pm), _hip.ptr(pn), _hip.ptr(zs),
-                                            _hip.ptr(dout), _hip.ptr(dxm), _hip.ptr(dxn), _hip.ptr(dpm), _hip.ptr(dpn),
-                                            _hip.ptr(dpre), R, D, C, _hip.stream()), "mmdfn_gated_pair_bwd")
+        _hip.call("mmdfn_gated_pair_bwd", _hip.ptr(xm), _hip.ptr(xn), _hip.ptr(w), _hip.ptr(pm), _hip.ptr(pn), _hip.ptr(zs),
+                  _hip.ptr(dout), _hip.ptr(dxm), _hip.ptr(dxn), _hip.ptr(dpm), _hip.ptr(dpn),
+                  _hip.ptr(dpre), R, D, C, _hip.stream())
         dwb = torch.empty(3 * D + 1, dtype=xm.dtype, device=xm.device)
-        _hip.check(lib.mmdfn_rowscale_colsum(_hip.ptr(dpre), _hip.ptr(xm), _hip.ptr(xn), _hip.ptr(dwb), R, D, _hip.stream()),
-                   "mmdfn_rowscale_colsum")
+        _hip.call("mmdfn_rowscale_colsum", _hip.ptr(dpre), _hip.ptr(xm), _hip.ptr(xn), _hip.ptr(dwb), R, D, _hip.stream())
         return dxm, dxn, dpm, dpn, dwb[:3 * D].view(1, 3 * D), dwb[3 * D:].view(1)
 
 
@@ -185,9 +183,9 @@ class _Lmf(torch.autograd.Function):
             linear_group_raw(c)
         w, bias = w.contiguous(), bias.contiguous()
         out = torch.empty(N, O, dtype=torch.float32, device=P.device)
-        _hip.check(_hip.lib().mmdfn_lmf_fwd(_hip.ptr(P), _hip.ptr(fs[0]), _hip.ptr(fs[1]), _hip.ptr(fs[2]), fs[0].stride(0),
-                                            fs[1].stride(0), fs[2].stride(0), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(out), N, O, R,
-                                            P.stride(0), O, _hip.stream()), "mmdfn_lmf_fwd")
+        _hip.call("mmdfn_lmf_fwd", _hip.ptr(P), _hip.ptr(fs[0]), _hip.ptr(fs[1]), _hip.ptr(fs[2]), fs[0].stride(0),
+                  fs[1].stride(0), fs[2].stride(0), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(out), N, O, R,
+                  P.stride(0), O, _hip.stream())
         ctx.save_for_backward(P, *hs, *fs, w)
         return out
 
@@ -197,11 +195,10 @@ class _Lmf(torch.autograd.Function):
         hs, fs = (ha, hv, ht), (fa, fv, ft)
         R, O, N = fa.shape[0], fa.shape[2], P.shape[0]
         g = g.contiguous()
-        lib = _hip.lib()
-        width = int(lib.mmdfn_lmf_bwd_width(O, R))
+        width = int(_hip.query("mmdfn_lmf_bwd_width", O, R))
         D = torch.empty(N, width, dtype=torch.float32, device=P.device)
-        _hip.check(lib.mmdfn_lmf_bwd(_hip.ptr(g), _hip.ptr(P), _hip.ptr(w), _hip.ptr(D), N, O, R, g.stride(0), P.stride(0),
-                                     D.stride(0), _hip.stream()), "mmdfn_lmf_bwd")
+        _hip.call("mmdfn_lmf_bwd", _hip.ptr(g), _hip.ptr(P), _hip.ptr(w), _hip.ptr(D), N, O, R, g.stride(0), P.stride(0),
+                  D.stride(0), _hip.stream())
         sums = _colsum_wide(D)       # (rank 5 and up at the default 300 outputs: more than one launch's 4096 columns)
         blk = lambda m, r: D[:, (m * R + r) * O:(m * R + r + 1) * O]
         dfs = [torch.empty_like(f) for f in fs]
@@ -228,8 +225,8 @@ def _tfn_rows(h):
     return h if h.stride(1) == 1 and h.stride(0) >= h.shape[1] else h.contiguous()
 
 
-def _tfn_workspace(lib, N, H, O, which, device):
-    n = int(lib.mmdfn_tfn_workspace(N, H[0], H[1], H[2], O, which))
+def _tfn_workspace(N, H, O, which, device):
+    n = int(_hip.query("mmdfn_tfn_workspace", N, H[0], H[1], H[2], O, which))
     if n < 0:
         raise ValueError("tfn_fuse: hidden widths %s with %d outputs are not taken by the kernels (at most 304 outputs; the three "
                          "[1, h] rows of 64 utterances must fit the LDS next to a weight tile)" % (tuple(H), O))
@@ -259,8 +256,7 @@ class _Tfn(torch.autograd.Function):
             W1 = W1.contiguous()
         b1 = b1.contiguous()
         p = float(p)
-        lib = _hip.lib()
-        ws = _tfn_workspace(lib, N, H, O, 0, ha.device)
+        ws = _tfn_workspace(N, H, O, 0, ha.device)
         drop = bool(training) and p > 0.0
         used = state = None
         counters = 0
@@ -270,10 +266,10 @@ class _Tfn(torch.autograd.Function):
         keep = max(0.0, 1.0 - p) if drop else 1.0
         scale = keep_scale(p) if drop else 1.0
         out = torch.empty(N, O, dtype=torch.float32, device=ha.device)
-        _hip.check(lib.mmdfn_tfn_fwd(_hip.ptr(hs[0]), _hip.ptr(hs[1]), _hip.ptr(hs[2]), hs[0].stride(0), hs[1].stride(0),
-                                     hs[2].stride(0), _hip.ptr(W1), W1.stride(0), _hip.ptr(b1), _hip.ptr(state), _hip.ptr(used),
-                                     counters, keep, scale, _hip.ptr(out), _hip.ptr(ws), N, H[0], H[1], H[2], O, int(bool(relu)),
-                                     _hip.stream()), "mmdfn_tfn_fwd")
+        _hip.call("mmdfn_tfn_fwd", _hip.ptr(hs[0]), _hip.ptr(hs[1]), _hip.ptr(hs[2]), hs[0].stride(0), hs[1].stride(0),
+                  hs[2].stride(0), _hip.ptr(W1), W1.stride(0), _hip.ptr(b1), _hip.ptr(state), _hip.ptr(used),
+                  counters, keep, scale, _hip.ptr(out), _hip.ptr(ws), N, H[0], H[1], H[2], O, int(bool(relu)),
+                  _hip.stream())
         ctx.keep, ctx.scale, ctx.relu, ctx.drop = keep, scale, bool(relu), drop
         ctx.save_for_backward(hs[0], hs[1], hs[2], W1, out if relu else None, used)
         ctx.used_state = used                        # (tests: the flags of this call through ops.tfn_keep_flags)
@@ -284,21 +280,19 @@ class _Tfn(torch.autograd.Function):
         ha, hv, ht, W1, y1, used = ctx.saved_tensors
         N, H, O, K = ha.shape[0], [ha.shape[1], hv.shape[1], ht.shape[1]], W1.shape[0], W1.shape[1]
         dy = dy.contiguous()
-        lib = _hip.lib()
-        ws = _tfn_workspace(lib, N, H, O, 1, dy.device)
+        ws = _tfn_workspace(N, H, O, 1, dy.device)
         dpre = torch.empty(N, O, dtype=torch.float32, device=dy.device)
         dhs = [torch.empty(N, h, dtype=torch.float32, device=dy.device) for h in H]
-        _hip.check(lib.mmdfn_tfn_bwd_input(_hip.ptr(dy), _hip.ptr(y1), int(ctx.relu), _hip.ptr(W1), W1.stride(0), _hip.ptr(ha),
-                                           _hip.ptr(hv), _hip.ptr(ht), ha.stride(0), hv.stride(0), ht.stride(0), _hip.ptr(used),
-                                           ctx.keep, ctx.scale, _hip.ptr(dpre), _hip.ptr(dhs[0]), _hip.ptr(dhs[1]),
-                                           _hip.ptr(dhs[2]), _hip.ptr(ws), N, H[0], H[1], H[2], O, _hip.stream()),
-                   "mmdfn_tfn_bwd_input")
+        _hip.call("mmdfn_tfn_bwd_input", _hip.ptr(dy), _hip.ptr(y1), int(ctx.relu), _hip.ptr(W1), W1.stride(0), _hip.ptr(ha),
+                  _hip.ptr(hv), _hip.ptr(ht), ha.stride(0), hv.stride(0), ht.stride(0), _hip.ptr(used),
+                  ctx.keep, ctx.scale, _hip.ptr(dpre), _hip.ptr(dhs[0]), _hip.ptr(dhs[1]),
+                  _hip.ptr(dhs[2]), _hip.ptr(ws), N, H[0], H[1], H[2], O, _hip.stream())
         dW1 = db1 = None
         if ctx.needs_input_grad[3]:
             dW1 = torch.empty(O, K, dtype=torch.float32, device=dy.device)
-            _hip.check(lib.mmdfn_tfn_bwd_weight(_hip.ptr(dpre), _hip.ptr(ha), _hip.ptr(hv), _hip.ptr(ht), ha.stride(0),
-                                                hv.stride(0), ht.stride(0), _hip.ptr(used), ctx.keep, ctx.scale, _hip.ptr(dW1), N,
-                                                H[0], H[1], H[2], O, _hip.stream()), "mmdfn_tfn_bwd_weight")
+            _hip.call("mmdfn_tfn_bwd_weight", _hip.ptr(dpre), _hip.ptr(ha), _hip.ptr(hv), _hip.ptr(ht), ha.stride(0),
+                      hv.stride(0), ht.stride(0), _hip.ptr(used), ctx.keep, ctx.scale, _hip.ptr(dW1), N,
+                      H[0], H[1], H[2], O, _hip.stream())
         if ctx.needs_input_grad[4]:
             db1 = colsum(dpre)
         return dhs[0], dhs[1], dhs[2], dW1, db1, None, None, None
@@ -315,6 +309,6 @@ def tfn_keep_flags(used_state, N, K, p, row0, rows):
     was ``used_state`` (2 int64 on the device: the tensor the call saved) applies to rows row0 .. row0 + rows - 1."""
     _hip.require_cuda(used_state)
     out = torch.empty(int(rows), int(K), dtype=torch.float32, device=used_state.device)
-    _hip.check(_hip.lib().mmdfn_tfn_keep_flags(_hip.ptr(used_state), max(0.0, 1.0 - float(p)), _hip.ptr(out), int(N), int(K),
-                                               int(row0), int(rows), _hip.stream()), "mmdfn_tfn_keep_flags")
+    _hip.call("mmdfn_tfn_keep_flags", _hip.ptr(used_state), max(0.0, 1.0 - float(p)), _hip.ptr(out), int(N), int(K),
+              int(row0), int(rows), _hip.stream())
     return out

@@ -19,10 +19,9 @@ def propagate_raw(tiles, cross, H, lay, transpose=False, out=None):
     d = H.shape[1]
     if out is None:
         out = torch.empty(H.shape[0], d, dtype=torch.float32, device=H.device)
-    rc = _hip.lib().mmdfn_propagate(_hip.ptr(tiles), _hip.ptr(cross), _hip.ptr(H), _hip.ptr(out), *_lay_args(lay),
-                                    lay.B, lay.M, lay.N, d, H.stride(0), out.stride(0), lay.max_len,
-                                    1 if transpose else 0, _hip.stream())
-    _hip.check(rc, "mmdfn_propagate")
+    _hip.call("mmdfn_propagate", _hip.ptr(tiles), _hip.ptr(cross), _hip.ptr(H), _hip.ptr(out), *_lay_args(lay),
+              lay.B, lay.M, lay.N, d, H.stride(0), out.stride(0), lay.max_len,
+              1 if transpose else 0, _hip.stream())
     return out
 
 
@@ -35,10 +34,9 @@ def tile_outer_raw(X, Y, lay, dtiles=None, dcross=None):
     if dtiles is None:
         dtiles = torch.empty(lay.tile_elems, dtype=torch.float32, device=X.device)
         dcross = torch.empty(lay.npairs, lay.N, dtype=torch.float32, device=X.device)
-    rc = _hip.lib().mmdfn_tile_outer(_hip.ptr(X), _hip.ptr(Y), _hip.ptr(dtiles), _hip.ptr(dcross), *_lay_args(lay),
-                                     lay.B, lay.M, lay.N, X.shape[1], X.stride(0), Y.stride(0), lay.max_len,
-                                     1 if accumulate else 0, _hip.stream())
-    _hip.check(rc, "mmdfn_tile_outer")
+    _hip.call("mmdfn_tile_outer", _hip.ptr(X), _hip.ptr(Y), _hip.ptr(dtiles), _hip.ptr(dcross), *_lay_args(lay),
+              lay.B, lay.M, lay.N, X.shape[1], X.stride(0), Y.stride(0), lay.max_len,
+              1 if accumulate else 0, _hip.stream())
     return dtiles, dcross
 
 
@@ -88,11 +86,10 @@ class _BuildAdjacency(torch.autograd.Function):
         rdeg = torch.empty(M, N, **f32)
         tiles = torch.empty(lay.tile_elems, **f32)
         cross = torch.empty(lay.npairs, N, **f32)
-        rc = _hip.lib().mmdfn_adj_build_kind(_hip.ptr(feats), _hip.ptr(unit), _hip.ptr(norm), _hip.ptr(cosg),
-                                             _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles), _hip.ptr(cross),
-                                             *_lay_args(lay), lay.B, M, N, D, lay.max_len, float(modal_weight),
-                                             int(kind), _hip.stream())
-        _hip.check(rc, "mmdfn_adj_build_kind")
+        _hip.call("mmdfn_adj_build_kind", _hip.ptr(feats), _hip.ptr(unit), _hip.ptr(norm), _hip.ptr(cosg),
+                  _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles), _hip.ptr(cross),
+                  *_lay_args(lay), lay.B, M, N, D, lay.max_len, float(modal_weight),
+                  int(kind), _hip.stream())
         ctx.lay = lay
         ctx.kind = int(kind)
         ctx.modal_weight = float(modal_weight)
@@ -119,13 +116,12 @@ class _BuildAdjacency(torch.autograd.Function):
         dunit = torch.empty_like(unit)
         dfeats = torch.empty_like(unit)
         addend = dalias.contiguous() if dalias is not None else None
-        rc = _hip.lib().mmdfn_adj_build_bwd_kind(_hip.ptr(dtiles), _hip.ptr(dcross), _hip.ptr(unit), _hip.ptr(norm),
-                                                 _hip.ptr(cosg), _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles),
-                                                 _hip.ptr(cross), _hip.ptr(wsym), _hip.ptr(etile), _hip.ptr(ecross),
-                                                 _hip.ptr(ddeg), _hip.ptr(dunit), _hip.ptr(dfeats), _hip.ptr(addend),
-                                                 *_lay_args(lay),
-                                                 lay.B, M, N, D, lay.max_len, ctx.modal_weight, ctx.kind, _hip.stream())
-        _hip.check(rc, "mmdfn_adj_build_bwd_kind")
+        _hip.call("mmdfn_adj_build_bwd_kind", _hip.ptr(dtiles), _hip.ptr(dcross), _hip.ptr(unit), _hip.ptr(norm),
+                  _hip.ptr(cosg), _hip.ptr(cdot), _hip.ptr(rdeg), _hip.ptr(tiles),
+                  _hip.ptr(cross), _hip.ptr(wsym), _hip.ptr(etile), _hip.ptr(ecross),
+                  _hip.ptr(ddeg), _hip.ptr(dunit), _hip.ptr(dfeats), _hip.ptr(addend),
+                  *_lay_args(lay),
+                  lay.B, M, N, D, lay.max_len, ctx.modal_weight, ctx.kind, _hip.stream())
         # the graph part of the backward pass ends here (the encoders' nodes follow): its queued weight gradients leave now
         flush_queued_wgrads_early()
         return dfeats, None, None, None
@@ -226,9 +222,8 @@ def build_band_adjacency(x, lengths, keys, width):
     f32 = dict(dtype=torch.float32, device=x.device)
     deg, rdeg = torch.empty(N, **f32), torch.empty(N, **f32)
     tiles = torch.empty(lay.tile_elems, **f32)
-    rc = _hip.lib().mmdfn_adj_build_band(_hip.ptr(feats), _hip.ptr(keys), _hip.ptr(deg), _hip.ptr(rdeg), _hip.ptr(tiles),
-                                         *_lay_args(lay), lay.B, 1, N, D, lay.max_len, int(width), _hip.stream())
-    _hip.check(rc, "mmdfn_adj_build_band")
+    _hip.call("mmdfn_adj_build_band", _hip.ptr(feats), _hip.ptr(keys), _hip.ptr(deg), _hip.ptr(rdeg), _hip.ptr(tiles),
+              *_lay_args(lay), lay.B, 1, N, D, lay.max_len, int(width), _hip.stream())
     adj = BlockTileAdjacency(lay, tiles, torch.empty(0, N, **f32), symmetric=True)
     adj.rdeg = rdeg
     return adj
@@ -282,9 +277,8 @@ class _LstmPointwise(torch.autograd.Function):
             c_prev = c_prev.contiguous()
         h = torch.empty(R, H, dtype=torch.float32, device=G.device)
         c = torch.empty_like(h)
-        rc = _hip.lib().mmdfn_lstm_pointwise_fwd(_hip.ptr(G), _hip.ptr(c_prev), _hip.ptr(h), _hip.ptr(c), R, H,
-                                                 _hip.stream())
-        _hip.check(rc, "mmdfn_lstm_pointwise_fwd")
+        _hip.call("mmdfn_lstm_pointwise_fwd", _hip.ptr(G), _hip.ptr(c_prev), _hip.ptr(h), _hip.ptr(c), R, H,
+                  _hip.stream())
         ctx.has_prev = c_prev is not None
         ctx.save_for_backward(G, c, *([c_prev] if c_prev is not None else []))
         return h, c
@@ -299,9 +293,8 @@ class _LstmPointwise(torch.autograd.Function):
         dc = dc.contiguous() if dc is not None else None
         dG = torch.empty_like(G)
         dcp = torch.empty_like(c)
-        rc = _hip.lib().mmdfn_lstm_pointwise_bwd(_hip.ptr(G), _hip.ptr(c_prev), _hip.ptr(c), _hip.ptr(dh),
-                                                 _hip.ptr(dc), _hip.ptr(dG), _hip.ptr(dcp), R, H, _hip.stream())
-        _hip.check(rc, "mmdfn_lstm_pointwise_bwd")
+        _hip.call("mmdfn_lstm_pointwise_bwd", _hip.ptr(G), _hip.ptr(c_prev), _hip.ptr(c), _hip.ptr(dh),
+                  _hip.ptr(dc), _hip.ptr(dG), _hip.ptr(dcp), R, H, _hip.stream())
         return dG, (dcp if ctx.has_prev else None)
 
 
@@ -321,9 +314,8 @@ class _GcniiCombine(torch.autograd.Function):
         q_ = q.contiguous() if q is not None else None
         mask_ = mask.contiguous() if mask is not None else None
         out = torch.empty_like(P)
-        rc = _hip.lib().mmdfn_gcnii_combine_fwd(_hip.ptr(P), _hip.ptr(S2), _hip.ptr(q_), _hip.ptr(mask_), _hip.ptr(out),
-                                                float(theta), float(alpha), R, d, _hip.stream())
-        _hip.check(rc, "mmdfn_gcnii_combine_fwd")
+        _hip.call("mmdfn_gcnii_combine_fwd", _hip.ptr(P), _hip.ptr(S2), _hip.ptr(q_), _hip.ptr(mask_), _hip.ptr(out),
+                  float(theta), float(alpha), R, d, _hip.stream())
         ctx.theta, ctx.alpha, ctx.has_mask, ctx.has_q = float(theta), float(alpha), mask is not None, q is not None
         ctx.save_for_backward(P, S2, *([mask_] if mask is not None else []))
         return out
@@ -337,9 +329,8 @@ class _GcniiCombine(torch.autograd.Function):
         R, d = P.shape
         dP = torch.empty_like(P)
         dS2 = torch.empty_like(S2)
-        rc = _hip.lib().mmdfn_gcnii_combine_bwd(_hip.ptr(P), _hip.ptr(S2), _hip.ptr(mask), _hip.ptr(dout), _hip.ptr(dP),
-                                                _hip.ptr(dS2), ctx.theta, ctx.alpha, R, d, _hip.stream())
-        _hip.check(rc, "mmdfn_gcnii_combine_bwd")
+        _hip.call("mmdfn_gcnii_combine_bwd", _hip.ptr(P), _hip.ptr(S2), _hip.ptr(mask), _hip.ptr(dout), _hip.ptr(dP),
+                  _hip.ptr(dS2), ctx.theta, ctx.alpha, R, d, _hip.stream())
         return dP, dS2, (dout if ctx.has_q else None), None, None, None
 
 

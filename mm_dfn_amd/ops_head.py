@@ -36,12 +36,11 @@ class _Head(torch.autograd.Function):
         mask = mask.contiguous() if mask is not None else None
         logp = torch.empty(N, C, dtype=torch.float32, device=Fm.device)
         if relu:
-            rc = _hip.lib().mmdfn_head_fwd(_hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(logp), N, Wd,
-                                           C, ldf, split, float(mscale), _hip.stream())
+            _hip.call("mmdfn_head_fwd", _hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(logp), N, Wd,
+                      C, ldf, split, float(mscale), _hip.stream())
         else:
-            rc = _hip.lib().mmdfn_head_fwd_act(_hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(logp), N,
-                                               Wd, C, ldf, split, float(mscale), 0, _hip.stream())
-        _hip.check(rc, "mmdfn_head_fwd")
+            _hip.call("mmdfn_head_fwd_act", _hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(logp), N,
+                      Wd, C, ldf, split, float(mscale), 0, _hip.stream())
         ctx.relu = bool(relu)
         ctx.mscale = float(mscale)
         ctx.dims = (N, Wd, split, ldf)
@@ -54,9 +53,8 @@ class _Head(torch.autograd.Function):
         N, Wd, split, ldf = ctx.dims
         C = weight.shape[0]
         dlogp = dlogp.contiguous()
-        lib = _hip.lib()
         dF = torch.empty(Fm.shape, dtype=torch.float32, device=Fm.device)
-        ws = torch.empty(int(lib.mmdfn_head_bwd_workspace(Wd, C)), dtype=torch.float32, device=Fm.device)
+        ws = torch.empty(int(_hip.query("mmdfn_head_bwd_workspace", Wd, C)), dtype=torch.float32, device=Fm.device)
         pw, pb = ctx.refs
         if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and tuple(pw.shape) == (C, Wd) and pw.is_contiguous()
                 and slab_reduce_queueable(pw, [pb])):
@@ -64,11 +62,10 @@ class _Head(torch.autograd.Function):
             args = (_hip.ptr(dlogp), _hip.ptr(logp), _hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(dF), _hip.ptr(ws),
                     N, Wd, C, ldf, split if split else Wd, split, ctx.mscale)
             if ctx.relu:
-                rc = lib.mmdfn_head_bwd_partial(*args, _hip.stream())
+                _hip.call("mmdfn_head_bwd_partial", *args, _hip.stream())
             else:
-                rc = lib.mmdfn_head_bwd_partial_act(*args, 0, _hip.stream())
-            _hip.check(rc, "mmdfn_head_bwd_partial")
-            G = int(lib.mmdfn_head_bwd_groups())
+                _hip.call("mmdfn_head_bwd_partial_act", *args, 0, _hip.stream())
+            G = int(_hip.query("mmdfn_head_bwd_groups"))
             queue_slab_reduce(ws[:G * C * Wd], ws[G * C * Wd:], G, C, Wd, weight=pw, biases=[pb])
             return dF, None, None, None, None, None
         dW = torch.empty(C, Wd, dtype=torch.float32, device=Fm.device)
@@ -76,10 +73,9 @@ class _Head(torch.autograd.Function):
         args = (_hip.ptr(dlogp), _hip.ptr(logp), _hip.ptr(Fm), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(dF), _hip.ptr(dW),
                 _hip.ptr(db), _hip.ptr(ws), N, Wd, C, ldf, split if split else Wd, split, ctx.mscale)
         if ctx.relu:
-            rc = lib.mmdfn_head_bwd(*args, _hip.stream())
+            _hip.call("mmdfn_head_bwd", *args, _hip.stream())
         else:
-            rc = lib.mmdfn_head_bwd_act(*args, 0, _hip.stream())
-        _hip.check(rc, "mmdfn_head_bwd")
+            _hip.call("mmdfn_head_bwd_act", *args, 0, _hip.stream())
         return dF, None, None, dW, db, None
 
 

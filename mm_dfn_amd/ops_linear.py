@@ -21,9 +21,8 @@ def linear_raw(x2d, weight, bias=None, act=0, out=None, accumulate=False):
     weight = weight.contiguous()
     if out is None:
         out = torch.empty(R, N, dtype=torch.float32, device=x2d.device)
-    rc = _hip.lib().mmdfn_linear(_hip.ptr(x2d), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out), R, K, N,
-                                 x2d.stride(0), out.stride(0), int(act), 1 if accumulate else 0, _hip.stream())
-    _hip.check(rc, "mmdfn_linear")
+    _hip.call("mmdfn_linear", _hip.ptr(x2d), _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(out), R, K, N,
+              x2d.stride(0), out.stride(0), int(act), 1 if accumulate else 0, _hip.stream())
     return out
 
 
@@ -92,27 +91,22 @@ def linear_group_raw(problems, act=0):
     _hip.require_f32(*X, *W)
     ia, pa = _hip.int_array, _hip.ptr_array
     if any(xb is not None for xb in X2):
-        rc = _hip.lib().mmdfn_linear_group_seg2(n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
-                                                ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), pa(X2), pa(WK2),
-                                                ia(K2), ia(ldx2), ia(ldw2), int(act), _hip.stream())
-        if rc == -2:
-            return None
-        _hip.check(rc, "mmdfn_linear_group_seg2")
-        return Y
+        rc = _hip.call("mmdfn_linear_group_seg2", n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
+                       ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), pa(X2), pa(WK2),
+                       ia(K2), ia(ldx2), ia(ldw2), int(act), _hip.stream(), allow=(-2,))
+        return None if rc == -2 else Y
     if any(z is not None for z in Z):
-        rc = _hip.lib().mmdfn_linear_group_addend(n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
-                                                  ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), int(act),
-                                                  _hip.stream())
-        _hip.check(rc, "mmdfn_linear_group_addend")
+        _hip.call("mmdfn_linear_group_addend", n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), pa(Z), ia(ldz), ia(R),
+                  ia(K), ia(N), ia(ldx), ia(ldw), ia(ldy), ia(km), ia(acc), int(act),
+                  _hip.stream())
         return Y
-    rc = _hip.lib().mmdfn_linear_group(n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), ia(R), ia(K), ia(N), ia(ldx),
-                                       ia(ldw), ia(ldy), ia(km), ia(acc), int(act), _hip.stream())
-    _hip.check(rc, "mmdfn_linear_group")
+    _hip.call("mmdfn_linear_group", n, pa(X), pa(W), pa(W2), ia(N1), pa(B1), pa(B2), pa(Y), ia(R), ia(K), ia(N), ia(ldx),
+              ia(ldw), ia(ldy), ia(km), ia(acc), int(act), _hip.stream())
     return Y
 
 
 def linear_group_supported(R, K, N):
-    return bool(_hip.lib().mmdfn_linear_group_supported(int(R), int(K), int(N)))
+    return bool(_hip.query("mmdfn_linear_group_supported", int(R), int(K), int(N)))
 
 
 def dense_nk(x2, weight, bias=None, act=0, out=None, accumulate=False):
@@ -399,9 +393,8 @@ class _Linear2(torch.autograd.Function):
             y = linear_group_raw([dict(x=x2, w=w1c, w2=w2c, b=b1, b2=b2)])[0]
         else:
             y = torch.empty(R, N, dtype=torch.float32, device=x2.device)
-            rc = _hip.lib().mmdfn_linear2(_hip.ptr(x2), _hip.ptr(w1c), _hip.ptr(w2c), n1, _hip.ptr(b1), _hip.ptr(b2), _hip.ptr(y),
-                                          R, K, N, x2.stride(0), N, 0, 0, _hip.stream())
-            _hip.check(rc, "mmdfn_linear2")
+            _hip.call("mmdfn_linear2", _hip.ptr(x2), _hip.ptr(w1c), _hip.ptr(w2c), n1, _hip.ptr(b1), _hip.ptr(b2), _hip.ptr(y),
+                      R, K, N, x2.stride(0), N, 0, 0, _hip.stream())
         ctx.refs = (w1, w2, b1, b2)
         ctx.save_for_backward(x2, w1c, w2c, wcat)
         return y.view(*shp[:-1], N)
@@ -480,11 +473,11 @@ def _cut_planes(entries):
     live = [(e, p[0], p[1]) for e, p in live if p is not None]
     for i in range(0, len(live), 16):
         chunk = live[i:i + 16]
-        rc = _hip.lib().mmdfn_cut_weight_planes(
+        _hip.call(
+            "mmdfn_cut_weight_planes",
             len(chunk), pa([w1 for _, w1, _ in chunk]), pa([w2 for _, _, w2 in chunk]), ia([e.n1 for e, _, _ in chunk]),
             ia([w1.stride(0) for _, w1, _ in chunk]), ia([e.N for e, _, _ in chunk]), ia([e.K for e, _, _ in chunk]),
             ia([e.mode for e, _, _ in chunk]), pa([e.buf for e, _, _ in chunk]), _hip.stream())
-        _hip.check(rc, "mmdfn_cut_weight_planes")
         for e, w1, w2 in chunk:
             e.epoch = _PLANE_EPOCH[0]
             e.stamp = _plane_stamp(w1, w2)
@@ -521,7 +514,7 @@ def weight_planes(w1, w2=None, transposed=False, mode=None):
             if w2 is not None and w2.shape[0] != w1.shape[0]:
                 raise ValueError("weight_planes: modes 2 / 3 need matrices with the same number of rows")
             e.N, e.K, e.n1 = cols + (0 if w2 is None else w2.shape[1]), w1.shape[0], cols
-        nbytes = _hip.lib().mmdfn_weight_planes_workspace(e.N, e.K)
+        nbytes = _hip.query("mmdfn_weight_planes_workspace", e.N, e.K)
         if nbytes <= 0:
             raise _hip.HipLibraryError("mmdfn_weight_planes_workspace refused N=%d K=%d" % (e.N, e.K))
         e.buf = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
@@ -587,9 +580,8 @@ def linear_planes_raw(x2, w1, w2=None, b1=None, b2=None, transposed=False, act=0
     if out is None:
         out = torch.empty(R, e.N, dtype=torch.float32, device=x2.device)
     n1 = e.N if (transposed or w2 is None) else e.n1      # (bias split: only the forward orientation has two bias blocks)
-    rc = _hip.lib().mmdfn_linear_planes(_hip.ptr(x2), _hip.ptr(e.buf), _hip.ptr(b1), _hip.ptr(b2), n1, _hip.ptr(out), R, K, e.N,
-                                        x2.stride(0), out.stride(0), int(act), 1 if accumulate else 0, _hip.stream())
-    _hip.check(rc, "mmdfn_linear_planes")
+    _hip.call("mmdfn_linear_planes", _hip.ptr(x2), _hip.ptr(e.buf), _hip.ptr(b1), _hip.ptr(b2), n1, _hip.ptr(out), R, K, e.N,
+              x2.stride(0), out.stride(0), int(act), 1 if accumulate else 0, _hip.stream())
     return out
 
 
@@ -604,7 +596,6 @@ def linear_planes_group_raw(problems, transposed=False, act=0, mask_scale=1.0, x
     they come first, one per modality, at most four problems in all) store their rows in party order into S instead of an output
     of their own (None in the returned list), and the launch also writes rank and the padding rows of S
     (mmdfn_linear_planes_group_party); returns None when the shape is not covered (nothing was launched)."""
-    lib = _hip.lib()
     xs, ents, outs = [], [], []
     for pr in problems:
         x2 = pr["x"]
@@ -641,32 +632,28 @@ def linear_planes_group_raw(problems, transposed=False, act=0, mask_scale=1.0, x
         pm = [pr.get("party_m", -1) if pr.get("party_m") is not None else -1 for pr in problems]
         Mn = sum(1 for v in pm if v >= 0)
         n1 = [e.N if pr.get("w2") is None else e.n1 for pr, e in zip(problems, ents)]
-        rc = lib.mmdfn_linear_planes_group_party(
-            len(problems), _hip.ptr_array(xs), _hip.ptr_array([e.buf for e in ents]),
+        rc = _hip.call(
+            "mmdfn_linear_planes_group_party", len(problems), _hip.ptr_array(xs), _hip.ptr_array([e.buf for e in ents]),
             _hip.ptr_array([pr.get("b1") for pr in problems]), _hip.ptr_array([pr.get("b2") for pr in problems]),
             _hip.int_array(n1), _hip.ptr_array(outs), _hip.int_array([x.shape[0] for x in xs]),
             _hip.int_array([e.K for e in ents]), _hip.int_array([e.N for e in ents]), _hip.int_array([x.stride(0) for x in xs]),
             _hip.int_array([0 if o is None else o.stride(0) for o in outs]), int(act), 0,
             _hip.ptr_array([pr.get("mask") for pr in problems]), float(mask_scale),
             _hip.ptr_array([pr.get("xmask") for pr in problems]), _hip.ptr_array([pr.get("xdrop") for pr in problems]),
-            float(xscale), _hip.int_array(pm), _hip.ptr(qm), _hip.ptr(S), _hip.ptr(rank), L, B, P, Mn, _hip.stream())
-        if rc == -2:
-            return None
-        _hip.check(rc, "mmdfn_linear_planes_group_party")
-        return outs
+            float(xscale), _hip.int_array(pm), _hip.ptr(qm), _hip.ptr(S), _hip.ptr(rank), L, B, P, Mn, _hip.stream(), allow=(-2,))
+        return None if rc == -2 else outs
     for i in range(0, len(problems), 4):
         sl = slice(i, i + 4)
         prs, x4, e4, o4 = problems[sl], xs[sl], ents[sl], outs[sl]
         n1 = [e.N if (transposed or pr.get("w2") is None) else e.n1 for pr, e in zip(prs, e4)]
-        rc = lib.mmdfn_linear_planes_group_in(len(prs), _hip.ptr_array(x4), _hip.ptr_array([e.buf for e in e4]),
-                                           _hip.ptr_array([pr.get("b1") for pr in prs]), _hip.ptr_array([pr.get("b2") for pr in prs]),
-                                           _hip.int_array(n1), _hip.ptr_array(o4), _hip.int_array([x.shape[0] for x in x4]),
-                                           _hip.int_array([e.K for e in e4]), _hip.int_array([e.N for e in e4]),
-                                           _hip.int_array([x.stride(0) for x in x4]), _hip.int_array([o.stride(0) for o in o4]),
-                                           int(act), 0, _hip.ptr_array([pr.get("mask") for pr in prs]), float(mask_scale),
-                                           _hip.ptr_array([pr.get("xmask") for pr in prs]),
-                                           _hip.ptr_array([pr.get("xdrop") for pr in prs]), float(xscale), _hip.stream())
-        _hip.check(rc, "mmdfn_linear_planes_group_in")
+        _hip.call("mmdfn_linear_planes_group_in", len(prs), _hip.ptr_array(x4), _hip.ptr_array([e.buf for e in e4]),
+                  _hip.ptr_array([pr.get("b1") for pr in prs]), _hip.ptr_array([pr.get("b2") for pr in prs]),
+                  _hip.int_array(n1), _hip.ptr_array(o4), _hip.int_array([x.shape[0] for x in x4]),
+                  _hip.int_array([e.K for e in e4]), _hip.int_array([e.N for e in e4]),
+                  _hip.int_array([x.stride(0) for x in x4]), _hip.int_array([o.stride(0) for o in o4]),
+                  int(act), 0, _hip.ptr_array([pr.get("mask") for pr in prs]), float(mask_scale),
+                  _hip.ptr_array([pr.get("xmask") for pr in prs]),
+                  _hip.ptr_array([pr.get("xdrop") for pr in prs]), float(xscale), _hip.stream())
     return outs
 
 

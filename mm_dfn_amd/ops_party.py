@@ -34,9 +34,8 @@ class _PartyGather(torch.autograd.Function):
         bias_ = bias.contiguous() if bias is not None else None
         S = torch.empty(L, Mn * B * P, H, dtype=torch.float32, device=qmask.device)
         rank = torch.empty(L, B, P, dtype=torch.int32, device=qmask.device)
-        rc = _hip.lib().mmdfn_party_gather(Mn, _hip.ptr_array(mods), _hip.ptr(qmask), _hip.ptr(bias_), _hip.ptr(S),
-                                           _hip.ptr(rank), L, B, P, H, _hip.stream())
-        _hip.check(rc, "mmdfn_party_gather")
+        _hip.call("mmdfn_party_gather", Mn, _hip.ptr_array(mods), _hip.ptr(qmask), _hip.ptr(bias_), _hip.ptr(S),
+                  _hip.ptr(rank), L, B, P, H, _hip.stream())
         ctx.dims = (L, B, P, H, Mn)
         ctx.stacked = stacked
         ctx.has_bias = bias is not None
@@ -57,9 +56,8 @@ class _PartyGather(torch.autograd.Function):
         dX = torch.empty(Mn, L, B, H, dtype=torch.float32, device=dev)
         held = [None if d is None else d.contiguous() for d in dpass]
         addend = _hip.ptr_array(held) if any(h is not None for h in held) else None
-        rc = _hip.lib().mmdfn_party_gather_bwd(Mn, _hip.ptr(dS), _hip.ptr(rank), _hip.ptr_array([dX[m] for m in range(Mn)]),
-                                               addend, L, B, P, H, _hip.stream())
-        _hip.check(rc, "mmdfn_party_gather_bwd")
+        _hip.call("mmdfn_party_gather_bwd", Mn, _hip.ptr(dS), _hip.ptr(rank), _hip.ptr_array([dX[m] for m in range(Mn)]),
+                  addend, L, B, P, H, _hip.stream())
         dbias = dS.sum((0, 1)) if ctx.has_bias and ctx.needs_input_grad[1] else None
         if ctx.stacked:
             return None, dbias, None, dX
@@ -91,12 +89,11 @@ def _queue_bias_halves(A, b1, b2, n1, slabs=None):
     if A.stride(1) != 1:
         A = A.contiguous()
     R, N = A.shape
-    lib = _hip.lib()
     if slabs is not None:
         ws, nsl = slabs
     else:
-        ws = torch.empty(int(lib.mmdfn_colsum_workspace(N)), dtype=torch.float32, device=A.device)
-        nsl = lib.mmdfn_colsum_partial(_hip.ptr(A), R, N, A.stride(0), _hip.ptr(ws), _hip.stream())
+        ws = torch.empty(int(_hip.query("mmdfn_colsum_workspace", N)), dtype=torch.float32, device=A.device)
+        nsl = _hip.query("mmdfn_colsum_partial", _hip.ptr(A), R, N, A.stride(0), _hip.ptr(ws), _hip.stream())
         if nsl <= 0:
             raise _hip.HipLibraryError("mmdfn_colsum_partial rejected the operand (%d)" % nsl)
     buf = torch.empty(N, dtype=torch.float32, device=A.device)
@@ -174,9 +171,8 @@ class _ProjectGather(torch.autograd.Function):
             bias = None
             if b1 is not None:
                 bias = bcat if bcat is not None else torch.cat([b1, b2])
-            rc = _hip.lib().mmdfn_party_gather(Mn, _hip.ptr_array([G[i] for i in range(Mn)]), _hip.ptr(qmask), _hip.ptr(bias),
-                                               _hip.ptr(S), _hip.ptr(rank), L, B, P, N, _hip.stream())
-            _hip.check(rc, "mmdfn_party_gather")
+            _hip.call("mmdfn_party_gather", Mn, _hip.ptr_array([G[i] for i in range(Mn)]), _hip.ptr(qmask), _hip.ptr(bias),
+                      _hip.ptr(S), _hip.ptr(rank), L, B, P, N, _hip.stream())
         ctx.dims = (L, B, P, H, Mn, n1, N)
         ctx.refs = (w1, w2, b1, b2)
         ctx.riders = [(src, tuple(pr[:4])) for (src, _), pr in zip(riders, rprm)]
@@ -202,19 +198,17 @@ class _ProjectGather(torch.autograd.Function):
         # biases' .grad are the halves (views handed over here, filled at the end of the backward pass)
         queue_db = (want_db and ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and slab_reduce_queueable(None, [b1, b2])
                     and b1.grad is None and b2.grad is None)
-        lib = _hip.lib()
         if queue_db:
             # the scatter and the column-sum slabs read the same dS: one launch
-            ws = torch.empty(int(lib.mmdfn_colsum_workspace(N)), dtype=torch.float32, device=dev)
-            nsl = lib.mmdfn_party_gather_bwd_colsum(Mn, _hip.ptr(dS), _hip.ptr(rank), _hip.ptr_array([dG[m] for m in range(Mn)]),
-                                                    None, L, B, P, N, _hip.ptr(ws), _hip.stream())
+            ws = torch.empty(int(_hip.query("mmdfn_colsum_workspace", N)), dtype=torch.float32, device=dev)
+            nsl = _hip.query("mmdfn_party_gather_bwd_colsum", Mn, _hip.ptr(dS), _hip.ptr(rank),
+                             _hip.ptr_array([dG[m] for m in range(Mn)]), None, L, B, P, N, _hip.ptr(ws), _hip.stream())
             if nsl <= 0:
                 raise _hip.HipLibraryError("mmdfn_party_gather_bwd_colsum rejected the operands (%d)" % nsl)
             _queue_bias_halves(dS.view(-1, N), b1, b2, n1, slabs=(ws, int(nsl)))
         else:
-            rc = lib.mmdfn_party_gather_bwd(Mn, _hip.ptr(dS), _hip.ptr(rank), _hip.ptr_array([dG[m] for m in range(Mn)]),
-                                            None, L, B, P, N, _hip.stream())
-            _hip.check(rc, "mmdfn_party_gather_bwd")
+            _hip.call("mmdfn_party_gather_bwd", Mn, _hip.ptr(dS), _hip.ptr(rank), _hip.ptr_array([dG[m] for m in range(Mn)]),
+                      None, L, B, P, N, _hip.stream())
         db1 = db2 = None
         if want_db and not queue_db:
             db = colsum(dS.view(-1, N))
@@ -344,9 +338,8 @@ class _PartyCombine(torch.autograd.Function):
         N = flat_idx.numel()
         E_ = E.contiguous() if E is not None else None
         out = torch.empty(Mn, N, H, dtype=torch.float32, device=rank.device)
-        rc = _hip.lib().mmdfn_party_combine(Mn, _hip.ptr_array(bases), _hip.ptr(E_), _hip.ptr(rank), _hip.ptr(flat_idx),
-                                            _hip.ptr(out), _hip.float_array(weights), L, B, P, N, H, _hip.stream())
-        _hip.check(rc, "mmdfn_party_combine")
+        _hip.call("mmdfn_party_combine", Mn, _hip.ptr_array(bases), _hip.ptr(E_), _hip.ptr(rank), _hip.ptr(flat_idx),
+                  _hip.ptr(out), _hip.float_array(weights), L, B, P, N, H, _hip.stream())
         ctx.dims = (L, B, P, H, Mn, N)
         ctx.weights = list(weights)
         ctx.has_E = E is not None
@@ -366,19 +359,16 @@ class _PartyCombine(torch.autograd.Function):
             buf = torch.empty(nb + ne, dtype=torch.float32, device=dout.device)
             dbase = buf[:nb].view(Mn, L, B, H)
             dE = buf[nb:].view(L, nact * B * P, H) if ctx.has_E else None
-            rc = _hip.lib().mmdfn_party_combine_bwd_dst(Mn, _hip.ptr(dout), _hip.ptr(rank), _hip.ptr(inv),
-                                                        _hip.ptr_array([dbase[m] for m in range(Mn)]), _hip.ptr(dE),
-                                                        _hip.float_array(ctx.weights), L, B, P, N, H, _hip.stream())
-            if rc != -2:
-                _hip.check(rc, "mmdfn_party_combine_bwd_dst")
+            rc = _hip.call("mmdfn_party_combine_bwd_dst", Mn, _hip.ptr(dout), _hip.ptr(rank), _hip.ptr(inv),
+                           _hip.ptr_array([dbase[m] for m in range(Mn)]), _hip.ptr(dE),
+                           _hip.float_array(ctx.weights), L, B, P, N, H, _hip.stream(), allow=(-2,))
         if rc == -2:
             zero = torch.zeros(nb + ne, dtype=torch.float32, device=dout.device)       # one fill for both (pad rows stay 0)
             dbase = zero[:nb].view(Mn, L, B, H)
             dE = zero[nb:].view(L, nact * B * P, H) if ctx.has_E else None
-            rc = _hip.lib().mmdfn_party_combine_bwd(Mn, _hip.ptr(dout), _hip.ptr(rank), _hip.ptr(flat_idx),
-                                                    _hip.ptr_array([dbase[m] for m in range(Mn)]), _hip.ptr(dE),
-                                                    _hip.float_array(ctx.weights), L, B, P, N, H, _hip.stream())
-            _hip.check(rc, "mmdfn_party_combine_bwd")
+            _hip.call("mmdfn_party_combine_bwd", Mn, _hip.ptr(dout), _hip.ptr(rank), _hip.ptr(flat_idx),
+                      _hip.ptr_array([dbase[m] for m in range(Mn)]), _hip.ptr(dE),
+                      _hip.float_array(ctx.weights), L, B, P, N, H, _hip.stream())
         return (dE, None, None, None, None) + tuple(dbase[m] for m in range(Mn))
 
 

@@ -17,10 +17,9 @@ def colsum(A):
     if A.stride(1) != 1:
         A = A.contiguous()
     R, H = A.shape
-    lib = _hip.lib()
-    ws = torch.empty(int(lib.mmdfn_colsum_workspace(H)), dtype=torch.float32, device=A.device)
+    ws = torch.empty(int(_hip.query("mmdfn_colsum_workspace", H)), dtype=torch.float32, device=A.device)
     out = torch.empty(H, dtype=torch.float32, device=A.device)
-    _hip.check(lib.mmdfn_colsum(_hip.ptr(A), R, H, A.stride(0), _hip.ptr(out), _hip.ptr(ws), _hip.stream()), "mmdfn_colsum")
+    _hip.call("mmdfn_colsum", _hip.ptr(A), R, H, A.stride(0), _hip.ptr(out), _hip.ptr(ws), _hip.stream())
     return out
 
 
@@ -44,14 +43,12 @@ def gemm_tn(A, B, want_colsum=False):
     B = _strided_rows(B)
     R, M = A.shape
     N = B.shape[1]
-    lib = _hip.lib()
-    splits = lib.mmdfn_gemm_tn_splits(R, M, N)
+    splits = _hip.query("mmdfn_gemm_tn_splits", R, M, N)
     C = torch.empty(M, N, dtype=torch.float32, device=A.device)
     colsum = torch.empty(M, dtype=torch.float32, device=A.device) if want_colsum else None
     ws = torch.empty(splits * (M * N + M), dtype=torch.float32, device=A.device)
-    rc = lib.mmdfn_gemm_tn(_hip.ptr(A), _hip.ptr(B), _hip.ptr(C), _hip.ptr(colsum), _hip.ptr(ws), R, M, N,
-                           A.stride(0), B.stride(0), N, splits, _hip.stream())
-    _hip.check(rc, "mmdfn_gemm_tn")
+    _hip.call("mmdfn_gemm_tn", _hip.ptr(A), _hip.ptr(B), _hip.ptr(C), _hip.ptr(colsum), _hip.ptr(ws), R, M, N,
+              A.stride(0), B.stride(0), N, splits, _hip.stream())
     return C, colsum
 
 
@@ -75,16 +72,14 @@ def gemm_tn_grouped(problems):
     for p, a, b, c in zip(problems, A, B, C):
         if b.shape[0] != a.shape[0] or tuple(c.shape) != (a.shape[1], b.shape[1]) or c.stride(1) != 1:
             raise ValueError("gemm_tn_grouped: inconsistent problem shapes")
-    lib = _hip.lib()
     ia = _hip.int_array
-    nws = lib.mmdfn_gemm_tn_grouped_workspace(n, ia(R), ia(M), ia(N))
+    nws = _hip.query("mmdfn_gemm_tn_grouped_workspace", n, ia(R), ia(M), ia(N))
     ws = torch.empty(int(nws), dtype=torch.float32, device=A[0].device)
     cs_arr = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in cs])
-    rc = lib.mmdfn_gemm_tn_grouped(n, _hip.ptr_array(A), _hip.ptr_array(B), _hip.ptr_array(C), cs_arr, ia(R), ia(M), ia(N),
-                                   ia([a.stride(0) for a in A]), ia([b.stride(0) for b in B]),
-                                   ia([c.stride(0) for c in C]), ia([int(p.get("shift", 0)) for p in problems]),
-                                   _hip.ptr(ws), _hip.stream())
-    _hip.check(rc, "mmdfn_gemm_tn_grouped")
+    _hip.call("mmdfn_gemm_tn_grouped", n, _hip.ptr_array(A), _hip.ptr_array(B), _hip.ptr_array(C), cs_arr, ia(R), ia(M), ia(N),
+              ia([a.stride(0) for a in A]), ia([b.stride(0) for b in B]),
+              ia([c.stride(0) for c in C]), ia([int(p.get("shift", 0)) for p in problems]),
+              _hip.ptr(ws), _hip.stream())
     return ws   # kept alive by the caller's frame until the launches are enqueued (stream-ordered allocator)
 
 
@@ -270,10 +265,10 @@ def stage_riders(rows, T):
     riders = _WGQ["riders"]
     if not (RIDERS and _WGQ["scope"] > 0 and _WGQ["outs"]) or _WGQ["rider_keep"]:
         return riders
-    idle = _hip.lib().mmdfn_gru_seq_bwd_idle_cus(len(rows), _hip.int_array(rows))
+    idle = _hip.query("mmdfn_gru_seq_bwd_idle_cus", len(rows), _hip.int_array(rows))
     if idle <= 0:
         return riders
-    step_s = 1e-9 * _hip.lib().mmdfn_gru_seq_bwd_step_ns(len(rows), _hip.int_array(rows))     # (0.75 us; the MFMA form 2.3)
+    step_s = 1e-9 * _hip.query("mmdfn_gru_seq_bwd_step_ns", len(rows), _hip.int_array(rows))     # (0.75 us; the MFMA form 2.3)
     budget = RIDER_BUDGET * idle * max(T) * step_s * _RIDER_FLOPS_PER_CU_S
     take, nseg, work = [], 0, 0.0
     for key, o in list(_WGQ["outs"].items()):
@@ -297,11 +292,12 @@ def finish_riders():
     """Behind the GRU backward launch: a staged batch the launch did not take (another kernel form) is issued now; the
     references that kept its operands and slabs alive are dropped (the launches are in the stream)."""
     if _WGQ["rider_keep"]:
-        rc = _hip.lib().mmdfn_wgrad_riders_flush(_WGQ["riders"], _hip.stream())
-        # the slabs are read again by the reduction launch that takes them in (the end-of-backward batch's): held until then
-        _WGQ["rider_held"].append(_WGQ["rider_keep"])
-        _WGQ["rider_keep"] = None
-        _hip.check(rc, "mmdfn_wgrad_riders_flush")
+        try:
+            _hip.call("mmdfn_wgrad_riders_flush", _WGQ["riders"], _hip.stream())
+        finally:
+            # the slabs are read again by the reduction launch that takes them in (the end-of-backward batch's): held until then
+            _WGQ["rider_held"].append(_WGQ["rider_keep"])
+            _WGQ["rider_keep"] = None
 
 
 def _drain_riders(discard=False):
@@ -309,9 +305,10 @@ def _drain_riders(discard=False):
     if _WGQ["rider_held"] or _WGQ["rider_keep"]:
         if _WGQ["rider_keep"] and not discard:
             finish_riders()
-        rc = _hip.lib().mmdfn_wgrad_riders_drain(_WGQ["riders"], _hip.stream(), 1 if discard else 0)
-        _WGQ["rider_held"], _WGQ["rider_keep"] = [], None
-        _hip.check(rc, "mmdfn_wgrad_riders_drain")
+        try:
+            _hip.call("mmdfn_wgrad_riders_drain", _WGQ["riders"], _hip.stream(), 1 if discard else 0)
+        finally:
+            _WGQ["rider_held"], _WGQ["rider_keep"] = [], None
 
 
 def flush_queued_wgrads_early():
@@ -501,7 +498,6 @@ def _launch_wgrad_batch(batch):
 def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
     """The launch (a function of the stream) of one weight-gradient batch; ``riders``: the rider context of the backward pass
     (``stage``: the batch is staged in it for the next GRU backward launch)."""
-    lib = _hip.lib()
     ia = _hip.int_array
     pa = lambda ts: (ctypes.c_void_p * max(1, len(ts)))(*[None if t is None else t.data_ptr() for t in ts])
     ext_items = ext_items or []
@@ -521,9 +517,8 @@ def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
             return lambda stream: None
 
         def call_ext(stream, _keep=ext_keep):
-            rc = lib.mmdfn_gemm_tn_batch_ext(0, None, None, None, None, None, None, None, 0, None, None, None, None, None, None,
-                                             None, None, *ext_args, riders, stream)
-            _hip.check(rc, "mmdfn_gemm_tn_batch_ext")
+            _hip.call("mmdfn_gemm_tn_batch_ext", 0, None, None, None, None, None, None, None, 0, None, None, None, None, None, None,
+                      None, None, *ext_args, riders, stream)
         return call_ext
     A, B, R, lda, ldb, sh, oi = [], [], [], [], [], [], []
     C, cs1, cs2, M, N, ldc, acc = [], [], [], [], [], [], []
@@ -537,21 +532,19 @@ def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
             sh.append(s_); oi.append(k)
     _hip.require_cuda(*A, *B)
     _hip.require_f32(*A, *B, *C)
-    nws = lib.mmdfn_gemm_tn_batch_workspace(len(A), ia(R), ia(oi), len(C), ia(M), ia(N))
+    nws = _hip.query("mmdfn_gemm_tn_batch_workspace", len(A), ia(R), ia(oi), len(C), ia(M), ia(N))
     if nws < 0:
         raise _hip.HipLibraryError("mmdfn_gemm_tn_batch_workspace rejected the batch")
     ws = torch.empty(int(nws), dtype=torch.float32, device=A[0].device)
 
     def call(stream, _keep=(A, B, C, cs1, cs2, ws, ext_items)):
         if ext_args is not None:
-            rc = lib.mmdfn_gemm_tn_batch_ext(len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
-                                             pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), *ext_args, riders, stream)
-            _hip.check(rc, "mmdfn_gemm_tn_batch_ext")
+            _hip.call("mmdfn_gemm_tn_batch_ext", len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
+                      pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), *ext_args, riders, stream)
             return
-        fn = lib.mmdfn_wgrad_riders_stage if stage else lib.mmdfn_gemm_tn_batch
-        rc = fn(len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
-                pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), riders, stream)
-        _hip.check(rc, "mmdfn_wgrad_riders_stage" if stage else "mmdfn_gemm_tn_batch")
+        _hip.call("mmdfn_wgrad_riders_stage" if stage else "mmdfn_gemm_tn_batch",
+                  len(A), pa(A), pa(B), ia(R), ia(lda), ia(ldb), ia(sh), ia(oi), len(C), pa(C), pa(cs1),
+                  pa(cs2), ia(M), ia(N), ia(ldc), ia(acc), _hip.ptr(ws), riders, stream)
     return call
 
 

@@ -67,7 +67,7 @@ class FlatAdam:
         host = _hip.AdamState(step=self._t, enabled=int(self._enabled), skip_nonfinite=int(self.skip_nonfinite), lr=lr,
                               weight_decay=wd, max_norm=self.max_grad_norm or 0.0, scale=1.0)
         words = torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32)
-        assert words.numel() * 4 == int(_hip.lib().mmdfn_adam_state_bytes())
+        assert words.numel() * 4 == int(_hip.query("mmdfn_adam_state_bytes"))
         self._state = words.to(device)
         self._partials = torch.zeros(self.PARTIALS, dtype=torch.float64, device=device)
         self._pushed = (lr, wd)
@@ -155,10 +155,9 @@ class FlatAdam:
             return self._step_device_state(g)
         self._t += 1
         grp = self.param_groups[0]
-        rc = _hip.lib().mmdfn_adam_step(_hip.ptr(self.flat_p), _hip.ptr(g), _hip.ptr(self.m), _hip.ptr(self.v),
-                                        g.numel(), float(grp["lr"]), self.betas[0], self.betas[1], self.eps,
-                                        float(grp["weight_decay"]), self._t, _hip.stream())
-        _hip.check(rc, "mmdfn_adam_step")
+        _hip.call("mmdfn_adam_step", _hip.ptr(self.flat_p), _hip.ptr(g), _hip.ptr(self.m), _hip.ptr(self.v),
+                  g.numel(), float(grp["lr"]), self.betas[0], self.betas[1], self.eps,
+                  float(grp["weight_decay"]), self._t, _hip.stream())
         # the kernel wrote the parameters behind autograd's version counters: piece planes cut from them are stale now
         from . import ops
         ops.invalidate_planes()
@@ -171,18 +170,15 @@ class FlatAdam:
             self._captured_args = (self.betas, self.eps)
         else:
             self._push_hyper()
-        lib, st, stream = _hip.lib(), _hip.ptr(self._state), _hip.stream()
+        st, stream = _hip.ptr(self._state), _hip.stream()
         partials, nparts = None, 0
         if self.max_grad_norm is not None or self.skip_nonfinite:
             count = ctypes.c_int(0)
-            rc = lib.mmdfn_grad_sumsq(_hip.ptr(g), g.numel(), _hip.ptr(self._partials), self.PARTIALS, ctypes.byref(count), stream)
-            _hip.check(rc, "mmdfn_grad_sumsq")
+            _hip.call("mmdfn_grad_sumsq", _hip.ptr(g), g.numel(), _hip.ptr(self._partials), self.PARTIALS, ctypes.byref(count), stream)
             partials, nparts = _hip.ptr(self._partials), count.value
-        rc = lib.mmdfn_adam_prepare(st, partials, nparts, self.betas[0], self.betas[1], stream)
-        _hip.check(rc, "mmdfn_adam_prepare")
-        rc = lib.mmdfn_adam_step_state(_hip.ptr(self.flat_p), _hip.ptr(g), _hip.ptr(self.m), _hip.ptr(self.v), g.numel(), st,
-                                       self.betas[0], self.betas[1], self.eps, stream)
-        _hip.check(rc, "mmdfn_adam_step_state")
+        _hip.call("mmdfn_adam_prepare", st, partials, nparts, self.betas[0], self.betas[1], stream)
+        _hip.call("mmdfn_adam_step_state", _hip.ptr(self.flat_p), _hip.ptr(g), _hip.ptr(self.m), _hip.ptr(self.v), g.numel(), st,
+                  self.betas[0], self.betas[1], self.eps, stream)
         if not capturing:
             # (a captured step's weights change at every REPLAY: CapturedStep.replay() invalidates behind its launch)
             from . import ops
