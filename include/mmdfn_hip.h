@@ -561,6 +561,45 @@ int mmdfn_gcnii_layer_bwd(const float* dout, const float* gmask, const float* W,
 int mmdfn_gcnii_layer_bwd_ld(const float* dout, const float* gmask, const float* W, float* dP, float* dhi, float* dh0,
                              float theta, float alpha, int R, int H, int lddo, int acc_h0, int lddhi, void* stream);
 
+/* Weight FRAGMENT IMAGES of the stack kernels (ABI 23, additive; csrc/stack_images.hip, csrc/stack_image_map.h).  Every
+ * workgroup of the launches above re-derives the same slice of a parameter (registers -> padded LDS rows) before its first
+ * MFMA.  The slice depends on the weights alone, so the caller may cut it ONCE per optimizer step into the order the
+ * consumer waves read it: float4 ((cb * ntiles + t) * nk + kc) * 64 + lane of an image is what lane `lane` of the wave that
+ * holds tile t of column block cb reads for K-chunk kc -- exact fp32 values of the parameter, or 0.0 where the LDS copy holds
+ * padding.  kind: 0 input fwd (W0), 1 input bwd (W0), 2 layer bwd (the (2H, H) weight), 3 gate fwd ([W_ih | W_hh]; has_h = 0:
+ * W_ih alone, the layer without a previous state), 4 gate bwd (W_ih column blocks, then W_hh's when has_h != 0).  F is read by
+ * kinds 0 / 1 only.
+ *   mmdfn_stack_images_workspace: bytes of one image (-1: shape not covered).
+ *   mmdfn_stack_image_source: host-side, no GPU work: the source of float j of image position (cb, t, kc, lane) -- returns 0
+ *     (the image holds 0.0), 1 (element (*row, *col) of the first matrix: W0 / W / W_ih) or 2 (of the second: W_hh); -1 on
+ *     arguments outside the image.  The cut kernel evaluates the same function.
+ *   mmdfn_cut_stack_images: n <= 16 images in ONE launch; parameters contiguous; w2 is W_hh for kinds 3 / 4 with has_h != 0
+ *     (else ignored, may be null); image[i]: 16-byte aligned, mmdfn_stack_images_workspace(...) bytes.
+ *   mmdfn_*_img: the launch without the suffix reading its weight slice from `image` (no slice in LDS: ~35 KB per workgroup
+ *     instead of ~120; the fragments are held in registers).  Results are bit-identical.  image = NULL: the entry without the
+ *     suffix.  Returns -2 (nothing launched) for shapes the image form does not cover (16 384 rows or more, F > 208): the caller takes
+ *     the entry without the suffix. */
+int64_t mmdfn_stack_images_workspace(int kind, int H, int F, int has_h);
+int mmdfn_stack_image_source(int kind, int H, int F, int has_h, int cb, int t, int kc, int lane, int j, int* row, int* col);
+int mmdfn_cut_stack_images(int n, const int* kind, const float* const* w1, const float* const* w2, const int* H, const int* F,
+                           const int* has_h, float* const* image, void* stream);
+int mmdfn_gcn_input_fwd_img(const float* x, const float* mx, const float* W0, const float* b0, const float* m0, float* xd,
+                            float* h0, float* cur0, int R, int F, int H, int ldxd, float mscale, const float* image,
+                            void* stream);
+int mmdfn_gcn_input_bwd_img(const float* dcur0, const float* m0, const float* dh0, const float* h0, const float* W0,
+                            const float* dxd, const float* mx, float* dpre, float* dx, int R, int F, int H, int lddxd,
+                            float mscale, const float* image, void* stream);
+int mmdfn_gcnii_layer_bwd_ld_img(const float* dout, const float* gmask, const float* W, float* dP, float* dhi, float* dh0,
+                                 float theta, float alpha, int R, int H, int lddo, int acc_h0, int lddhi, const float* image,
+                                 void* stream);
+int mmdfn_lstm_gate_fwd_pre_img(const float* q, const float* h, const float* c, const float* Wih, const float* Whh,
+                                const float* bsum, const float* bsum2, float* gates, float* h_out, float* c_out, int R, int H,
+                                int ldh, const float* planes, const float* image, void* stream);
+int mmdfn_lstm_gate_bwd_img(const float* gates, const float* c_prev, const float* c_new, const float* dh_a, const float* dh_b,
+                            const float* dc_next, const float* Wih, const float* Whh, const float* dres, float* dG,
+                            float* dc_prev, float* dq, float* dh_prev, int R, int H, int has_h, int lddres,
+                            const float* image, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Batch form: EVERY weight-gradient contraction of a training step in one launch pair (they feed nothing but the
  * optimizer, so the host queues them during backward and issues them at its end; run_train_erc.py:208 autograd).

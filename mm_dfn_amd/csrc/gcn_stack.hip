@@ -30,6 +30,7 @@
 // batches (cfg5: ~10^5 rows) keep the unfused path whose contractions run on the bf16-piece pipeline.
 #include "mmdfn_internal.h"
 #include "../../include/mmdfn_hip.h"
+#include "stack_image_map.h"
 #include <stdlib.h>
 
 namespace {
@@ -201,29 +202,84 @@ __device__ __forceinline__ void spill_tiles(const f32x4 (&acc)[NT], const int (&
     }
 }
 
+// Image forms (template parameter IMG of the kernels below): the B fragments of a wave's NT tiles come from the weight's
+// fragment image (stack_image_map.h; cut once per optimizer step by stack_images.hip) instead of a slice that every workgroup
+// parks in LDS -- one coalesced 1 KB request per (tile, chunk), all of them issued at the top of the kernel and HELD in
+// registers (nk * NT <= 26 float4 per lane) for every row block of the workgroup.  No sW, no stager registers, no pad fill.
+template <int NT, int NKM>
+struct ImageFrags {
+    float4 b[NT][NKM];
+    // tile0[t] = first LDS weight row of tile t (wrow0 of the staging form); cb = column block of the launch
+    __device__ __forceinline__ void load(const float4* __restrict__ img, const int (&tile0)[NT], int ntiles, int cb, int nk) {
+        const int lane = threadIdx.x & 63;
+        const float4* p[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) p[t] = img + ((int64_t)(cb * ntiles + (tile0[t] >> 4)) * nk) * 64 + lane;
+        // chunk-major: the memory counter is in order, so the first chunk's MFMAs wait for NT requests, not for all of them
+#pragma unroll
+        for (int kc = 0; kc < NKM; ++kc)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) b[t][kc] = kc < nk ? p[t][kc * 64] : zero4();
+    }
+};
+
+// contract() with the B side in registers: same A fragments from LDS, same MFMA order per accumulator (kc, then j) and the same
+// operand values, so the accumulators are bit-identical to contract()'s.
+template <int NT, int NKM>
+__device__ __forceinline__ void contract_img(f32x4 (&acc)[NT], const ImageFrags<NT, NKM>& w, const float* sA, int lda, int K) {
+    const int lane = threadIdx.x & 63, fi = lane & 15, g = lane >> 4;
+    const float* ap = sA + frag_row(fi) * lda + 4 * frag_unit(g);
+    const int nk = (K + 15) >> 4;
+    float4 a_n = ld4(ap);
+#pragma unroll
+    for (int kc = 0; kc < NKM; ++kc) {
+        if (kc < nk) {                                  // uniform
+            const float4 a_c = a_n;
+            if (kc + 1 < nk) a_n = ld4(ap + 16 * (kc + 1));
+            const float av[4] = {a_c.x, a_c.y, a_c.z, a_c.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const float4 bq = w.b[t][kc];
+                    const float bv = (j == 0) ? bq.x : (j == 1) ? bq.y : (j == 2) ? bq.z : bq.w;
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv, acc[t], 0, 0, 0);
+                }
+        }
+    }
+}
+
+constexpr int INPUT_FWD_NKM = 13;    // K chunks the held fragments of the input forward cover: F <= 208 (2 tiles x 13 = 26 float4)
+constexpr int STACK_H_NKM = 7;       // ... of the kernels that contract over H <= 100 (4 tiles x 7 = 28 float4)
+constexpr int GATE_FWD_NKM = 13;     // ... of the gate forward: K = 2 H <= 200 (2 tiles x 13)
+constexpr int GATE_BWD_NKM = 25;     // ... of the gate backward: K = 4 H <= 400 (1 tile x 25)
+
 #define FOR_ROW_BLOCKS(rb, nrb) for (int rb = blockIdx.x; rb < (nrb); rb += gridDim.x)
 
 // ------------------------------------------------------------------------------------------------------------------
 // input stage:  x_d = x (.) m_x * ms (written to xd, row stride ldxd);  h0 = relu(x_d W0^T + b0);  cur0 = h0 (.) m_0 * ms
 //   x (R, F) contiguous, W0 (H, F) nn.Linear layout; masks are 0 / 1 keep flags (scaled by ms) or null (= ones).
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gcn_input_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mx,
+// ONE (image form only): the grid has a workgroup per row block -- no next block to request or park
+template <bool IMG, bool ONE = false>
+__global__ __launch_bounds__(256, IMG ? 2 : 1) void gcn_input_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mx,
                                                             const float* __restrict__ W0, const float* __restrict__ b0,
                                                             const float* __restrict__ m0, float* __restrict__ xd,
                                                             float* __restrict__ h0, float* __restrict__ cur0, int R,
-                                                            int F, int H, int ldxd, float ms) {
+                                                            int F, int H, int ldxd, float ms, const float4* __restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ldw = lds_stride(F), ldp = ((H + 15) & ~15) + 4;   // whole 16-column tiles fit a row of sP
-    float* sW = smem;                         // [H][ldw]
-    float* sA = sW + H * ldw;                 // [2][16][ldw]
+    float* sW = smem;                         // [H][ldw]   (IMG: absent)
+    float* sA = IMG ? smem : sW + H * ldw;    // [2][16][ldw]
     float* sP = sA + 2 * RB * ldw;            // [16][ldp]
+    int wrow0[2];
+    const int nt = wave_tiles<2>(wrow0, (H + 15) >> 4);
     WeightStager<false> wst;
-    wst.issue(W0, F, 0, H, F);
+    ImageFrags<2, IMG ? INPUT_FWD_NKM : 1> wim;
+    if constexpr (!IMG) wst.issue(W0, F, 0, H, F);
     const int nrb = (R + RB - 1) / RB;
     const int F4 = F >> 2, H4 = H >> 2;
     const float rF4 = 1.0f / (float)F4, rH4 = 1.0f / (float)H4;
-    int wrow0[2];
-    const int nt = wave_tiles<2>(wrow0, (H + 15) >> 4);
     constexpr int NS = 4;                     // float4 slots per thread per block (16 * F / 4 / 256 <= 4 for F <= 256)
     constexpr int NE = 2;                     // epilogue slots (16 * H / 4 / 256 <= 2)
     float4 rx[NS], rm[NS];
@@ -250,14 +306,16 @@ __global__ __launch_bounds__(256) void gcn_input_fwd_kernel(const float* __restr
     };
     const int rb0 = blockIdx.x;
     if (rb0 < nrb) issue(rb0);
-    wst.commit(sW, ldw, H, F);
+    // (behind the block's own rows: parking them waits for nothing the fragments have in flight)
+    if constexpr (IMG) wim.load(img, wrow0, (H + 15) >> 4, 0, (F + 15) >> 4);
+    if constexpr (!IMG) wst.commit(sW, ldw, H, F);
     zero_pads(sA, 2 * RB, ldw, F);
     if (rb0 < nrb) park(rb0, sA);
     __syncthreads();
     int buf = 0;
     FOR_ROW_BLOCKS(rb, nrb) {
         const int nxt = rb + gridDim.x;
-        if (nxt < nrb) issue(nxt);
+        if constexpr (!ONE) { if (nxt < nrb) issue(nxt); }
         float4 em[NE], eb[NE];
 #pragma unroll
         for (int s = 0; s < NE; ++s) {
@@ -268,7 +326,8 @@ __global__ __launch_bounds__(256) void gcn_input_fwd_kernel(const float* __restr
             eb[s] = (ok && b0) ? ld4(b0 + n) : zero4();
         }
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        contract<2>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, F);
+        if constexpr (IMG) contract_img(acc, wim, sA + buf * RB * ldw, ldw, F);
+        else contract<2>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, F);
         spill_tiles<2>(acc, wrow0, nt, sP, ldp);
         __syncthreads();
 #pragma unroll
@@ -281,7 +340,7 @@ __global__ __launch_bounds__(256) void gcn_input_fwd_kernel(const float* __restr
             st4(h0 + (int64_t)row * H + n, v);
             st4(cur0 + (int64_t)row * H + n, mul4(v, scl4(em[s], m0 ? ms : 1.0f)));
         }
-        if (nxt < nrb) park(nxt, sA + (buf ^ 1) * RB * ldw);
+        if constexpr (!ONE) { if (nxt < nrb) park(nxt, sA + (buf ^ 1) * RB * ldw); }
         __syncthreads();
         buf ^= 1;
     }
@@ -290,23 +349,26 @@ __global__ __launch_bounds__(256) void gcn_input_fwd_kernel(const float* __restr
 // backward of the input stage:
 //   dpre = (dcur0 (.) m_0 ms + dh0) (.) [h0 > 0]       (written out: operand of the weight gradients)
 //   dx   = (dpre W0 + dxd) (.) m_x ms                    dxd = gradient reaching x_d directly (row stride lddxd), may be null
-__global__ __launch_bounds__(256) void gcn_input_bwd_kernel(const float* __restrict__ dcur0, const float* __restrict__ m0,
+template <bool IMG, bool ONE = false>
+__global__ __launch_bounds__(256, ONE ? 2 : 1) void gcn_input_bwd_kernel(const float* __restrict__ dcur0, const float* __restrict__ m0,
                                                             const float* __restrict__ dh0, const float* __restrict__ h0,
                                                             const float* __restrict__ W0, const float* __restrict__ dxd,
                                                             const float* __restrict__ mx, float* __restrict__ dpre,
-                                                            float* __restrict__ dx, int R, int F, int H, int lddxd, float ms) {
+                                                            float* __restrict__ dx, int R, int F, int H, int lddxd, float ms,
+                                                            const float4* __restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ldw = lds_stride(H), ldp = ((F + 15) & ~15) + 4;
-    float* sW = smem;                         // [F][ldw]  (dx = dpre . W0: output column n, contraction index k < H)
-    float* sA = sW + F * ldw;                 // [2][16][ldw]
+    float* sW = smem;                         // [F][ldw]  (dx = dpre . W0: output column n, contraction index k < H; IMG: absent)
+    float* sA = IMG ? smem : sW + F * ldw;    // [2][16][ldw]
     float* sP = sA + 2 * RB * ldw;            // [16][ldp]
+    int wrow0[4];
+    const int nt = wave_tiles<4>(wrow0, (F + 15) >> 4);
     WeightStager<true> wst;
-    wst.issue(W0, F, 0, F, H);
+    ImageFrags<4, IMG ? STACK_H_NKM : 1> wim;
+    if constexpr (!IMG) wst.issue(W0, F, 0, F, H);
     const int nrb = (R + RB - 1) / RB;
     const int H4 = H >> 2, F4 = F >> 2;
     const float rF4 = 1.0f / (float)F4, rH4 = 1.0f / (float)H4;
-    int wrow0[4];
-    const int nt = wave_tiles<4>(wrow0, (F + 15) >> 4);
     constexpr int NS = 2;                     // 16 * H / 4 / 256 <= 2 for H <= 128
     constexpr int NE = 4;                     // 16 * F / 4 / 256 <= 4
     float4 rd[NS], rmk[NS], rh0[NS], rdh[NS];
@@ -337,14 +399,15 @@ __global__ __launch_bounds__(256) void gcn_input_bwd_kernel(const float* __restr
         }
     };
     if ((int)blockIdx.x < nrb) issue(blockIdx.x);
-    wst.commit(sW, ldw, F, H);
+    if constexpr (IMG) wim.load(img, wrow0, (F + 15) >> 4, 0, (H + 15) >> 4);
+    if constexpr (!IMG) wst.commit(sW, ldw, F, H);
     zero_pads(sA, 2 * RB, ldw, H);
     if ((int)blockIdx.x < nrb) park(blockIdx.x, sA);
     __syncthreads();
     int buf = 0;
     FOR_ROW_BLOCKS(rb, nrb) {
         const int nxt = rb + gridDim.x;
-        if (nxt < nrb) issue(nxt);
+        if constexpr (!ONE) { if (nxt < nrb) issue(nxt); }
         float4 ed[NE], em[NE];
 #pragma unroll
         for (int s = 0; s < NE; ++s) {
@@ -357,7 +420,8 @@ __global__ __launch_bounds__(256) void gcn_input_bwd_kernel(const float* __restr
         f32x4 acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        contract<4>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, H);
+        if constexpr (IMG) contract_img(acc, wim, sA + buf * RB * ldw, ldw, H);
+        else contract<4>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, H);
         spill_tiles<4>(acc, wrow0, nt, sP, ldp);
         __syncthreads();
 #pragma unroll
@@ -367,7 +431,7 @@ __global__ __launch_bounds__(256) void gcn_input_bwd_kernel(const float* __restr
             if (i >= RB * F4 || row >= R) continue;
             st4(dx + (int64_t)row * F + n, mul4(add4(ld4(sP + r * ldp + n), ed[s]), scl4(em[s], mx ? ms : 1.0f)));
         }
-        if (nxt < nrb) park(nxt, sA + (buf ^ 1) * RB * ldw);
+        if constexpr (!ONE) { if (nxt < nrb) park(nxt, sA + (buf ^ 1) * RB * ldw); }
         __syncthreads();
         buf ^= 1;
     }
@@ -667,16 +731,17 @@ __global__ __launch_bounds__(512) void gcnii_layer_fwd_ws_kernel(const float* __
     if (producer && prev_rb >= 0) epilogue(prev_rb, sA + (buf ^ 1) * RB * ldw, sP + (buf ^ 1) * RB * ldp);
 }
 
+template <bool IMG>
 __global__ __launch_bounds__(512) void gcnii_layer_bwd_ws_kernel(const float* __restrict__ dout, const float* __restrict__ gmask,
                                                                  const float* __restrict__ W, float* __restrict__ dP,
                                                                  float* __restrict__ dhi, float* __restrict__ dh0,
                                                                  float theta, float alpha, int R, int H, int lddo, int acc_h0,
-                                                                 int lddhi) {
+                                                                 int lddhi, const float4* __restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int N = 2 * H;
     const int ldw = lds_stride(H), ldp = ((N + 15) & ~15) + 4;
-    float* sW = smem;                         // [2H][ldw]
-    float* sA = sW + N * ldw;                 // [2][16][ldw]   rows dP
+    float* sW = smem;                         // [2H][ldw]   (IMG: absent)
+    float* sA = IMG ? smem : sW + N * ldw;    // [2][16][ldw]   rows dP
     float* sP = sA + 2 * RB * ldw;            // [2][16][ldp]
     const int nrb = (R + RB - 1) / RB;
     const int H4 = H >> 2;
@@ -728,12 +793,19 @@ __global__ __launch_bounds__(512) void gcnii_layer_bwd_ws_kernel(const float* __
             st4(dh0 + (int64_t)row * H + n, add4(fma4(dp, c2, ld4(P + r * ldp + H + n)), eo[s]));
         }
     };
+    int wrow0[4];
+    const int nt = wave_tiles<4>(wrow0, (N + 15) >> 4);        // (consumer waves: threadIdx.x >> 6 = 0..3)
+    ImageFrags<4, IMG ? STACK_H_NKM : 1> wim;
     if (producer) {
         if (first < nrb) { issue(first); issue_epi(first); }
     } else {
-        WeightStager<false> wst;
-        wst.issue(W, H, 0, N, H);
-        wst.commit(sW, ldw, N, H);
+        if constexpr (IMG) {
+            wim.load(img, wrow0, (N + 15) >> 4, 0, (H + 15) >> 4);
+        } else {
+            WeightStager<false> wst;
+            wst.issue(W, H, 0, N, H);
+            wst.commit(sW, ldw, N, H);
+        }
         zero_pads(sA, 2 * RB, ldw, H);
     }
     if (producer) {
@@ -741,8 +813,6 @@ __global__ __launch_bounds__(512) void gcnii_layer_bwd_ws_kernel(const float* __
         if (first + stride < nrb) issue(first + stride);
     }
     __syncthreads();
-    int wrow0[4];
-    const int nt = wave_tiles<4>(wrow0, (N + 15) >> 4);
     int buf = 0, prev_rb = -1;
     for (int rb = first; rb < nrb; rb += stride) {
         const int nxt = rb + stride;
@@ -757,7 +827,8 @@ __global__ __launch_bounds__(512) void gcnii_layer_bwd_ws_kernel(const float* __
             f32x4 acc[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            contract<4>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, H);
+            if constexpr (IMG) contract_img(acc, wim, sA + buf * RB * ldw, ldw, H);
+            else contract<4>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, H);
             spill_tiles<4>(acc, wrow0, nt, sP + buf * RB * ldp, ldp);
         }
         __syncthreads();
@@ -1040,7 +1111,7 @@ __global__ __launch_bounds__(256) void lstm_gate_bwd_kernel(const float* __restr
 // fragments held in REGISTERS (<= 26 float4 per lane: K = 4 H <= 416, loaded once per workgroup straight from the parameter); the first tile
 // comes from the LDS slice as before, both share the A fragments.
 // ------------------------------------------------------------------------------------------------------------------
-template <int ABL, bool WIDE = false>
+template <int ABL, bool WIDE = false, bool IMG = false>
 __global__ __launch_bounds__(512) void lstm_gate_bwd_ws_kernel(const float* __restrict__ gates, const float* __restrict__ c_prev,
                                                                const float* __restrict__ c_new, const float* __restrict__ dh_a,
                                                                const float* __restrict__ dh_b, const float* __restrict__ dc_next,
@@ -1048,12 +1119,13 @@ __global__ __launch_bounds__(512) void lstm_gate_bwd_ws_kernel(const float* __re
                                                                const float* __restrict__ dres, float* __restrict__ dG,
                                                                float* __restrict__ dc_prev, float* __restrict__ dq,
                                                                float* __restrict__ dh_prev, int R, int H, int has_h,
-                                                               int lddres) {
+                                                               int lddres, const float4* __restrict__ img) {
+    static_assert(!(IMG && WIDE), "the image form keeps the two-column-block launch");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int K = 4 * H;
     const int ldw = lds_stride(K);
-    float* sW = smem;                                  // [CBW][ldw]
-    float* sA = sW + CBW * ldw;                        // [2][16][ldw]   rows dG
+    float* sW = smem;                                  // [CBW][ldw]   (IMG: absent)
+    float* sA = IMG ? smem : sW + CBW * ldw;           // [2][16][ldw]   rows dG
     const int nb = WIDE ? 1 : (H + CBW - 1) / CBW;
     const bool is_dh = (int)blockIdx.y >= nb;
     const int n0 = WIDE ? 0 : (is_dh ? blockIdx.y - nb : blockIdx.y) * CBW;
@@ -1069,7 +1141,16 @@ __global__ __launch_bounds__(512) void lstm_gate_bwd_ws_kernel(const float* __re
     const float rH4 = 1.0f / (float)H4;
     // ---- prologue: all 512 threads park the weight slice (k-contiguous rows sW[n][k] from the (K, H) parameter); all of a
     // thread's loads (<= 13 slots) go out before its first LDS store
-    {
+    // IMG: consumer wave w holds the fragments of tile w of its column block's image instead, requested first of all
+    ImageFrags<1, IMG ? GATE_BWD_NKM : 1> wim;
+    if constexpr (IMG) {
+        const int cw = tid >> 6;
+        const int tile0[1] = {16 * cw < ncols ? 16 * cw : 0};
+        if (!producer) wim.load(img, tile0, CBW / 16, blockIdx.y, (K + 15) >> 4);
+        const int np4 = (ldw - K) >> 2;
+        const float rnp4 = 1.0f / (float)(np4 > 0 ? np4 : 1);
+        for (int i = threadIdx.x; i < 2 * RB * np4; i += 512) { const int r = qdiv(i, rnp4), j = i - r * np4; st4(sA + r * ldw + K + 4 * j, zero4()); }
+    } else {
         const float* Wsrc = is_dh ? Whh : Wih;
         const int inner = ncols >> 2;                  // 16-byte slots per source row (k)
         const int total = K * inner;
@@ -1256,7 +1337,8 @@ __global__ __launch_bounds__(512) void lstm_gate_bwd_ws_kernel(const float* __re
                     }
                 }
             } else {
-                if (!(ABL & 1)) contract<1>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, K);
+                if constexpr (IMG) contract_img(acc, wim, sA + buf * RB * ldw, ldw, K);
+                else if (!(ABL & 1)) contract<1>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, K);
                 else acc[0][0] = sA[buf * RB * ldw + fi * ldw + g];
             }
             if (ecol_ok && !(ABL & 8)) {
@@ -1275,16 +1357,18 @@ __global__ __launch_bounds__(512) void lstm_gate_bwd_ws_kernel(const float* __re
 // K8 forward, producer / consumer form (see the backward above): waves 0-3 contract A(i) (wave = gate, both unit tiles) and
 // leave the pre-activations in sE[i & 1]; waves 4-7 run the cell math of block i - 1 from the other sE buffer and store
 // gates / c' / h', park A(i + 1) and keep block i + 2's rows in flight.  One barrier per block.
+template <bool IMG>
 __global__ __launch_bounds__(512) void lstm_gate_fwd_ws_kernel(const float* __restrict__ q, const float* __restrict__ h,
                                                                const float* __restrict__ c, const float* __restrict__ Wih,
                                                                const float* __restrict__ Whh, const float* __restrict__ bsum, const float* __restrict__ bsum2,
                                                                float* __restrict__ gates, float* __restrict__ h_out,
-                                                               float* __restrict__ c_out, int R, int H, int ldh) {
+                                                               float* __restrict__ c_out, int R, int H, int ldh,
+                                                               const float4* __restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int K = h ? 2 * H : H;
     const int ldw = lds_stride(K), lde = UB + 4;
-    float* sW = smem;                                  // [4 gates][UB][ldw]
-    float* sA = sW + 4 * UB * ldw;                     // [2][16][ldw]   rows [q | h]
+    float* sW = smem;                                  // [4 gates][UB][ldw]   (IMG: absent)
+    float* sA = IMG ? smem : sW + 4 * UB * ldw;        // [2][16][ldw]   rows [q | h]
     float* sE = sA + 2 * RB * ldw;                     // [2][4 gates][16][lde] pre-activations
     const int u0 = blockIdx.y * UB;
     const int nu = min(UB, H - u0);
@@ -1292,10 +1376,20 @@ __global__ __launch_bounds__(512) void lstm_gate_fwd_ws_kernel(const float* __re
     const float rH4 = 1.0f / (float)H4;
     const int tid = threadIdx.x & 255;
     const bool producer = threadIdx.x >= 256;
+    const int w = tid >> 6;
+    const int wrow0[2] = {w * UB, w * UB + 16};        // consumer wave = gate, both unit tiles
+    // IMG: the consumer waves' fragments of the column block's image, requested before anything else of the launch
+    ImageFrags<2, IMG ? GATE_FWD_NKM : 1> wim;
+    if constexpr (IMG) {
+        if (!producer) wim.load(img, wrow0, 4 * UB / 16, blockIdx.y, (K + 15) >> 4);
+        const int np4 = (ldw - K) >> 2;
+        const float rnp4 = 1.0f / (float)(np4 > 0 ? np4 : 1);
+        for (int i = threadIdx.x; i < 2 * RB * np4; i += 512) { const int r = qdiv(i, rnp4), j = i - r * np4; st4(sA + r * ldw + K + 4 * j, zero4()); }
+    }
     // ---- prologue (all 512 threads): weight rows (gate, ul) <- [W_ih | W_hh] row gate * H + u0 + ul; missing units: zeros.
     // Every load of the slice goes out before the first LDS store (7 + 7 slots per thread, unconditional loads from clamped
     // addresses: one memory round trip for the slice, not one per slot)
-    {
+    if constexpr (!IMG) {
         const int total = 4 * UB * H4;
         constexpr int NW2 = 7;                             // 4 gates x 32 units x (H / 4 <= 25) / 512 threads
         float4 vi[NW2], vh[NW2];
@@ -1391,8 +1485,6 @@ __global__ __launch_bounds__(512) void lstm_gate_fwd_ws_kernel(const float* __re
         if (first + stride < nrb) issue(first + stride);
     }
     __syncthreads();
-    const int w = tid >> 6;
-    const int wrow0[2] = {w * UB, w * UB + 16};        // consumer wave = gate, both unit tiles
     int buf = 0, prev_rb = -1;
     for (int rb = first; rb < nrb; rb += stride) {
         const int nxt = rb + stride;
@@ -1405,7 +1497,8 @@ __global__ __launch_bounds__(512) void lstm_gate_fwd_ws_kernel(const float* __re
             }
         } else {
             f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            contract<2>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, K);
+            if constexpr (IMG) contract_img(acc, wim, sA + buf * RB * ldw, ldw, K);
+            else contract<2>(acc, wrow0, sA + buf * RB * ldw, ldw, sW, ldw, K);
             const int lane = tid & 63, fi = lane & 15, g = lane >> 4;
             float* E = sE + buf * 4 * RB * lde;
 #pragma unroll
@@ -1475,8 +1568,8 @@ extern "C" int mmdfn_gcn_input_fwd(const float* x, const float* mx, const float*
                                    void* stream) {
     if (bad_dims(R, H) || F < 4 || (F & 3) || F > 256 || ldxd < F || (ldxd & 3)) return -1;
     const size_t lds = ((size_t)(H + 2 * RB) * lds_stride(F) + RB * (((H + 15) & ~15) + 4)) * sizeof(float);
-    LAUNCH_BIG_LDS(gcn_input_fwd_kernel, dim3(row_groups(R, 1)), lds, stream, x, mx, W0, b0, m0, xd, h0, cur0, R, F, H, ldxd,
-                   mscale);
+    LAUNCH_BIG_LDS(gcn_input_fwd_kernel<false>, dim3(row_groups(R, 1)), lds, stream, x, mx, W0, b0, m0, xd, h0, cur0, R, F, H, ldxd,
+                   mscale, (const float4*)nullptr);
     return 0;
 }
 
@@ -1485,8 +1578,8 @@ extern "C" int mmdfn_gcn_input_bwd(const float* dcur0, const float* m0, const fl
                                    float mscale, void* stream) {
     if (bad_dims(R, H) || F < 4 || (F & 3) || F > 256 || (dxd && (lddxd < F || (lddxd & 3)))) return -1;
     const size_t lds = ((size_t)(F + 2 * RB) * lds_stride(H) + RB * (((F + 15) & ~15) + 4)) * sizeof(float);
-    LAUNCH_BIG_LDS(gcn_input_bwd_kernel, dim3(row_groups(R, 1)), lds, stream, dcur0, m0, dh0, h0, W0, dxd, mx, dpre, dx, R, F, H,
-                   lddxd, mscale);
+    LAUNCH_BIG_LDS(gcn_input_bwd_kernel<false>, dim3(row_groups(R, 1)), lds, stream, dcur0, m0, dh0, h0, W0, dxd, mx, dpre, dx, R, F, H,
+                   lddxd, mscale, (const float4*)nullptr);
     return 0;
 }
 
@@ -1528,9 +1621,9 @@ static int lstm_gate_fwd_impl(const float* q, const float* h, const float* c, co
     if (gate_ws(R)) {
         const size_t ldsw = ((size_t)(4 * UB + 2 * RB) * lds_stride(h ? 2 * H : H) + 2 * 4 * RB * (UB + 4)) * sizeof(float);
         if (ldsw > 156 * 1024) return -1;
-        if (int e_ = mmdfn_allow_big_lds(lstm_gate_fwd_ws_kernel)) return e_;
-        hipLaunchKernelGGL(lstm_gate_fwd_ws_kernel, dim3(row_groups(R, ncb), ncb), dim3(512), ldsw, (hipStream_t)stream, q, h, c, Wih,
-                           Whh, bsum, bsum2, gates, h_out, c_out, R, H, ldh);
+        if (int e_ = mmdfn_allow_big_lds(lstm_gate_fwd_ws_kernel<false>)) return e_;
+        hipLaunchKernelGGL(lstm_gate_fwd_ws_kernel<false>, dim3(row_groups(R, ncb), ncb), dim3(512), ldsw, (hipStream_t)stream, q, h, c, Wih,
+                           Whh, bsum, bsum2, gates, h_out, c_out, R, H, ldh, (const float4*)nullptr);
         MMDFN_CHECK_LAUNCH();
         return 0;
     }
@@ -1563,7 +1656,7 @@ extern "C" int mmdfn_lstm_gate_bwd(const float* gates, const float* c_prev, cons
         if (int e_ = mmdfn_allow_big_lds(lstm_gate_bwd_ws_kernel<A_>)) return e_;                                            \
         hipLaunchKernelGGL(lstm_gate_bwd_ws_kernel<A_>, dim3(row_groups(R, ncb), ncb), dim3(512), ldsw, (hipStream_t)stream, \
                            gates, c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h, \
-                           lddres);                                                                                          \
+                           lddres, (const float4*)nullptr);                                                                                      \
         MMDFN_CHECK_LAUNCH();                                                                                                \
         return 0;
         if (const char* e = getenv("MMDFN_GATE_ABL")) {
@@ -1584,13 +1677,15 @@ extern "C" int mmdfn_lstm_gate_bwd(const float* gates, const float* c_prev, cons
             const int ncw = has_h ? 2 : 1;
             if (int e_ = mmdfn_allow_big_lds(lstm_gate_bwd_ws_kernel<0, true>)) return e_;
             hipLaunchKernelGGL((lstm_gate_bwd_ws_kernel<0, true>), dim3(row_groups(R, ncw), ncw), dim3(512), ldsw, (hipStream_t)stream,
-                               gates, c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h, lddres);
+                               gates, c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h, lddres,
+                               (const float4*)nullptr);
             MMDFN_CHECK_LAUNCH();
             return 0;
         }
         if (int e_ = mmdfn_allow_big_lds(lstm_gate_bwd_ws_kernel<0>)) return e_;
         hipLaunchKernelGGL(lstm_gate_bwd_ws_kernel<0>, dim3(row_groups(R, ncb), ncb), dim3(512), ldsw, (hipStream_t)stream, gates,
-                           c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h, lddres);
+                           c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h, lddres,
+                           (const float4*)nullptr);
         MMDFN_CHECK_LAUNCH();
         return 0;
     }
@@ -1625,9 +1720,9 @@ extern "C" int mmdfn_gcnii_layer_bwd_ld(const float* dout, const float* gmask, c
     if (layer_ws(R)) {
         const size_t ldsw = ((size_t)(2 * H + 2 * RB) * lds_stride(H) + 2 * RB * (((2 * H + 15) & ~15) + 4)) * sizeof(float);
         if (ldsw > 156 * 1024) return -1;
-        if (int e_ = mmdfn_allow_big_lds(gcnii_layer_bwd_ws_kernel)) return e_;
-        hipLaunchKernelGGL(gcnii_layer_bwd_ws_kernel, dim3(row_groups(R, 1)), dim3(512), ldsw, (hipStream_t)stream, dout, gmask, W,
-                           dP, dhi, dh0, theta, alpha, R, H, lddo, acc_h0, lddhi);
+        if (int e_ = mmdfn_allow_big_lds(gcnii_layer_bwd_ws_kernel<false>)) return e_;
+        hipLaunchKernelGGL(gcnii_layer_bwd_ws_kernel<false>, dim3(row_groups(R, 1)), dim3(512), ldsw, (hipStream_t)stream, dout, gmask, W,
+                           dP, dhi, dh0, theta, alpha, R, H, lddo, acc_h0, lddhi, (const float4*)nullptr);
         MMDFN_CHECK_LAUNCH();
         return 0;
     }
@@ -1640,4 +1735,122 @@ extern "C" int mmdfn_gcnii_layer_bwd_ld(const float* dout, const float* gmask, c
 extern "C" int mmdfn_gcnii_layer_bwd(const float* dout, const float* gmask, const float* W, float* dP, float* dhi, float* dh0,
                                      float theta, float alpha, int R, int H, int lddo, int acc_h0, void* stream) {
     return mmdfn_gcnii_layer_bwd_ld(dout, gmask, W, dP, dhi, dh0, theta, alpha, R, H, lddo, acc_h0, H, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Image forms (ABI 23, additive): the same launches with the weight slice taken from a fragment image that the caller cut
+// with mmdfn_cut_stack_images (stack_images.hip).  image = NULL is the entry without the suffix; -2 = the image form does
+// not cover the shape (nothing was launched: the caller takes the entry without the suffix).  Results are bit-identical.
+// Which launches of the stack node take their image form is the caller's choice (gcn_stack.STACK_IMAGE_KERNELS).
+// No weight slice sits in LDS (~35 KB per workgroup instead of ~120); every kernel holds its waves' fragments in registers
+// across the row blocks of the workgroup.
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The input kernels' image forms fit two workgroups on a compute unit when a workgroup has ONE row block (no next block's
+// operands in registers: 181 / 238 VGPRs, launch bound 2 waves per SIMD, 34 / 28 KB of LDS): all 330 blocks of cfg2 are
+// resident.  The 8-wave layer kernel needs more than 256 registers per two waves, so one workgroup per compute unit walks
+// its row blocks as in the staging form.
+constexpr int INPUT_FWD_IMG_BLOCKS = 1, INPUT_BWD_IMG_BLOCKS = 1, LAYER_BWD_IMG_BLOCKS = 2;
+// row blocks per workgroup of the image forms of the input / layer kernels (tuning build: MMDFN_STACK_IMG_BLOCKS)
+inline int img_row_groups(int R, int per) {
+    const int nrb = (R + RB - 1) / RB;
+#ifdef MMDFN_TUNING
+    if (const char* e = getenv("MMDFN_STACK_IMG_BLOCKS")) per = atoi(e) > 0 ? atoi(e) : 1;
+#endif
+    return (nrb + per - 1) / per;                   // (R <= STACK_IMG_MAX_ROWS: at most 1 024 workgroups)
+}
+
+inline bool bad_image(const float* image) { return ((uintptr_t)image & 15) != 0; }
+
+// The image forms are the dialogue-graph sizes' (cfg2-cfg4: 5 280-10 560 rows, one or two rounds of resident workgroups);
+// longer launches (cfg5; the many-row forms of the gate kernels start at 16 384 rows) keep the forms they were tuned with.
+constexpr int STACK_IMG_MAX_ROWS = 16383;
+
+}  // namespace
+
+extern "C" int mmdfn_gcn_input_fwd_img(const float* x, const float* mx, const float* W0, const float* b0, const float* m0,
+                                       float* xd, float* h0, float* cur0, int R, int F, int H, int ldxd, float mscale,
+                                       const float* image, void* stream) {
+    if (!image) return mmdfn_gcn_input_fwd(x, mx, W0, b0, m0, xd, h0, cur0, R, F, H, ldxd, mscale, stream);
+    if (bad_dims(R, H) || F < 4 || (F & 3) || F > 256 || ldxd < F || (ldxd & 3) || bad_image(image)) return -1;
+    if (R > STACK_IMG_MAX_ROWS || (F + 15) / 16 > INPUT_FWD_NKM) return -2;
+    const size_t lds = ((size_t)(2 * RB) * lds_stride(F) + RB * (((H + 15) & ~15) + 4)) * sizeof(float);
+    const int groups = img_row_groups(R, INPUT_FWD_IMG_BLOCKS);
+    if (groups == (R + RB - 1) / RB) {
+        LAUNCH_BIG_LDS((gcn_input_fwd_kernel<true, true>), dim3(groups), lds, stream, x, mx, W0, b0, m0, xd, h0, cur0, R, F, H, ldxd,
+                       mscale, reinterpret_cast<const float4*>(image));
+        return 0;
+    }
+    LAUNCH_BIG_LDS(gcn_input_fwd_kernel<true>, dim3(groups), lds, stream, x, mx, W0, b0, m0, xd, h0, cur0, R, F, H, ldxd, mscale,
+                   reinterpret_cast<const float4*>(image));
+    return 0;
+}
+
+extern "C" int mmdfn_gcn_input_bwd_img(const float* dcur0, const float* m0, const float* dh0, const float* h0, const float* W0,
+                                       const float* dxd, const float* mx, float* dpre, float* dx, int R, int F, int H,
+                                       int lddxd, float mscale, const float* image, void* stream) {
+    if (!image) return mmdfn_gcn_input_bwd(dcur0, m0, dh0, h0, W0, dxd, mx, dpre, dx, R, F, H, lddxd, mscale, stream);
+    if (bad_dims(R, H) || F < 4 || (F & 3) || F > 256 || (dxd && (lddxd < F || (lddxd & 3))) || bad_image(image)) return -1;
+    if (R > STACK_IMG_MAX_ROWS) return -2;
+    const size_t lds = ((size_t)(2 * RB) * lds_stride(H) + RB * (((F + 15) & ~15) + 4)) * sizeof(float);
+    const int groups = img_row_groups(R, INPUT_BWD_IMG_BLOCKS);
+    if (groups == (R + RB - 1) / RB) {
+        LAUNCH_BIG_LDS((gcn_input_bwd_kernel<true, true>), dim3(groups), lds, stream, dcur0, m0, dh0, h0, W0, dxd, mx, dpre, dx, R, F, H,
+                       lddxd, mscale, reinterpret_cast<const float4*>(image));
+        return 0;
+    }
+    LAUNCH_BIG_LDS(gcn_input_bwd_kernel<true>, dim3(groups), lds, stream, dcur0, m0, dh0, h0, W0, dxd, mx, dpre, dx, R, F, H, lddxd,
+                   mscale, reinterpret_cast<const float4*>(image));
+    return 0;
+}
+
+extern "C" int mmdfn_gcnii_layer_bwd_ld_img(const float* dout, const float* gmask, const float* W, float* dP, float* dhi,
+                                            float* dh0, float theta, float alpha, int R, int H, int lddo, int acc_h0, int lddhi,
+                                            const float* image, void* stream) {
+    if (!image) return mmdfn_gcnii_layer_bwd_ld(dout, gmask, W, dP, dhi, dh0, theta, alpha, R, H, lddo, acc_h0, lddhi, stream);
+    if (bad_dims(R, H) || lddo < H || (lddo & 3) || lddhi < H || (lddhi & 3) || !(theta > 0.f) || bad_image(image)) return -1;
+    if (R > STACK_IMG_MAX_ROWS) return -2;         // (below: the producer / consumer kernel at every R, its results are the 4-wave kernel's bits)
+    const size_t ldsw = ((size_t)(2 * RB) * lds_stride(H) + 2 * RB * (((2 * H + 15) & ~15) + 4)) * sizeof(float);
+    if (int e_ = mmdfn_allow_big_lds(gcnii_layer_bwd_ws_kernel<true>)) return e_;
+    hipLaunchKernelGGL(gcnii_layer_bwd_ws_kernel<true>, dim3(img_row_groups(R, LAYER_BWD_IMG_BLOCKS)), dim3(512), ldsw, (hipStream_t)stream, dout, gmask,
+                       W, dP, dhi, dh0, theta, alpha, R, H, lddo, acc_h0, lddhi, reinterpret_cast<const float4*>(image));
+    MMDFN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmdfn_lstm_gate_fwd_pre_img(const float* q, const float* h, const float* c, const float* Wih, const float* Whh,
+                                           const float* bsum, const float* bsum2, float* gates, float* h_out, float* c_out,
+                                           int R, int H, int ldh, const float* planes, const float* image, void* stream) {
+    if (!image) return mmdfn_lstm_gate_fwd_pre(q, h, c, Wih, Whh, bsum, bsum2, gates, h_out, c_out, R, H, ldh, planes, stream);
+    if (bad_dims(R, H) || (h == nullptr) != (c == nullptr) || ldh < H || (ldh & 3) || bad_image(image)) return -1;
+    if (R > STACK_IMG_MAX_ROWS || gate_split(R, H)) return -2;
+    const int ncb = (H + UB - 1) / UB;
+    const size_t ldsw = ((size_t)(2 * RB) * lds_stride(h ? 2 * H : H) + 2 * 4 * RB * (UB + 4)) * sizeof(float);
+    if (int e_ = mmdfn_allow_big_lds(lstm_gate_fwd_ws_kernel<true>)) return e_;
+    hipLaunchKernelGGL(lstm_gate_fwd_ws_kernel<true>, dim3(row_groups(R, ncb), ncb), dim3(512), ldsw, (hipStream_t)stream, q, h, c,
+                       Wih, Whh, bsum, bsum2, gates, h_out, c_out, R, H, ldh, reinterpret_cast<const float4*>(image));
+    MMDFN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmdfn_lstm_gate_bwd_img(const float* gates, const float* c_prev, const float* c_new, const float* dh_a,
+                                       const float* dh_b, const float* dc_next, const float* Wih, const float* Whh,
+                                       const float* dres, float* dG, float* dc_prev, float* dq, float* dh_prev, int R, int H,
+                                       int has_h, int lddres, const float* image, void* stream) {
+    if (!image)
+        return mmdfn_lstm_gate_bwd(gates, c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R, H, has_h,
+                                   lddres, stream);
+    if (bad_dims(R, H) || (has_h && (dc_prev == nullptr || dh_prev == nullptr || c_prev == nullptr)) || bad_image(image)) return -1;
+    if (dres != nullptr && (lddres < H || (lddres & 3))) return -1;
+    if (R > STACK_IMG_MAX_ROWS) return -2;
+    const int nb = (H + CBW - 1) / CBW;
+    const int ncb = has_h ? 2 * nb : nb;
+    const size_t ldsw = (size_t)(2 * RB) * lds_stride(4 * H) * sizeof(float);
+    if (int e_ = mmdfn_allow_big_lds(lstm_gate_bwd_ws_kernel<0, false, true>)) return e_;
+    hipLaunchKernelGGL((lstm_gate_bwd_ws_kernel<0, false, true>), dim3(row_groups(R, ncb), ncb), dim3(512), ldsw,
+                       (hipStream_t)stream, gates, c_prev, c_new, dh_a, dh_b, dc_next, Wih, Whh, dres, dG, dc_prev, dq, dh_prev, R,
+                       H, has_h, lddres, reinterpret_cast<const float4*>(image));
+    MMDFN_CHECK_LAUNCH();
+    return 0;
 }

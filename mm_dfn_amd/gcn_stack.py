@@ -17,6 +17,17 @@ import math
 
 PRECUT = __import__("os").environ.get("MMDFN_GATE_PRECUT", "1") == "1"     # (0: A/B aid, every workgroup cuts the cell's weights itself)
 FUSE_PROP_LAYER = __import__("os").environ.get("MMDFN_FUSE_PROP_LAYER", "1") == "1"   # (0: A/B aid, propagate and the layer update as two launches)
+# weight slices of the dense stack kernels from fragment images cut once per optimizer step (csrc/stack_images.hip; the
+# registry of ops_linear) instead of being re-derived by every workgroup (0: A/B aid, the staging path; same bits either way)
+# MMDFN_STACK_IMAGES: 1 (default) = the kernels below, 0 = none, "all", or a comma-separated list of kernel names.
+_SI = __import__("os").environ.get("MMDFN_STACK_IMAGES", "1")
+STACK_IMAGES = _SI != "0"
+STACK_IMAGE_ALL = ("input_fwd", "input_bwd", "layer_bwd", "gate_fwd", "gate_bwd")
+# on by default: the kernels whose image form beat the staging form by more than the staging form's own min-max spread in the
+# cfg2 kernel trace (profiles/r10_stack_weight_images.md).  The layer backward and the two gate kernels did not (0.1 and
+# 0.8-2.5 us against spreads of 1.6-6.6 us): they keep the staging path, their image forms stay selectable.
+STACK_IMAGE_KERNELS = frozenset(("input_fwd", "input_bwd") if _SI in ("0", "1") else
+                                STACK_IMAGE_ALL if _SI == "all" else [k for k in _SI.split(",") if k in STACK_IMAGE_ALL])
 
 import torch
 
@@ -35,6 +46,18 @@ def eligible(x, nfeat, nhidden, nlayers, params, lamda=1.0):
     return (x.is_cuda and x.dtype == torch.float32 and x.shape[0] <= ROW_LIMIT and nlayers >= 1 and lamda > 0
             and nhidden % 4 == 0 and 4 <= nhidden <= 100 and nfeat % 4 == 0 and 4 <= nfeat <= 256
             and (not torch.is_grad_enabled() or all(ops._leaf(p) for p in params)))
+
+
+STACK_IMAGE_MAX_ROWS = 16383  # the image forms are the dialogue-graph sizes' (the *_img entries answer -2 beyond it)
+
+
+def _image(kind, R, w1, w2=None, F=0):
+    """Device pointer of the fragment image of a kernel's weight slice, or None (switch off / shape not covered): the launch
+    then runs its staging form.  Asked for at every launch: the registry re-cuts an image whose weights changed."""
+    if not STACK_IMAGES or kind not in STACK_IMAGE_KERNELS or R > STACK_IMAGE_MAX_ROWS:
+        return None
+    e = ops.stack_image(kind, w1, w2, F)
+    return None if e is None else e.buf
 
 
 class _GcnStack(torch.autograd.Function):
@@ -58,7 +81,10 @@ class _GcnStack(torch.autograd.Function):
         xd = out if use_residue else new(R, F)                 # x_d lives in the left F columns of the residue output
         ldxd = F + H if use_residue else F
         h0, cur = new(R, H), new(R, H)
-        _hip.call("mmdfn_gcn_input_fwd", P(x), P(mx), P(W0), P(b0), P(m0), P(xd), P(h0), P(cur), R, F, H, ldxd, mscale, st)
+        img = _image("input_fwd", R, W0, F=F)
+        if img is None or _hip.call("mmdfn_gcn_input_fwd_img", P(x), P(mx), P(W0), P(b0), P(m0), P(xd), P(h0), P(cur), R, F, H, ldxd,
+                                    mscale, P(img), st, allow=(-2,)) == -2:
+            _hip.call("mmdfn_gcn_input_fwd", P(x), P(mx), P(W0), P(b0), P(m0), P(xd), P(h0), P(cur), R, F, H, ldxd, mscale, st)
         h = c = None
         layers = []
         # the layers' hidden states are column blocks of ONE (R, nl H) buffer: what every layer propagates (zin_l) is then the
@@ -75,8 +101,11 @@ class _GcnStack(torch.autograd.Function):
             rec = dict(q=q, h_prev=h, c_prev=c)
             if reason:
                 gates, h_new, c_new = new(R, 4 * H), zin_all[:, i * H:(i + 1) * H], new(R, H)
-                _hip.call("mmdfn_lstm_gate_fwd_pre", P(q), P(h), P(c), P(w_ih), P(w_hh), P(b_ih), P(b_hh), P(gates), P(h_new),
-                          P(c_new), R, H, nl * H, P(planes), st)
+                img = _image("gate_fwd", R, w_ih, None if h is None else w_hh)
+                if img is None or _hip.call("mmdfn_lstm_gate_fwd_pre_img", P(q), P(h), P(c), P(w_ih), P(w_hh), P(b_ih), P(b_hh),
+                                            P(gates), P(h_new), P(c_new), R, H, nl * H, P(planes), P(img), st, allow=(-2,)) == -2:
+                    _hip.call("mmdfn_lstm_gate_fwd_pre", P(q), P(h), P(c), P(w_ih), P(w_hh), P(b_ih), P(b_hh), P(gates), P(h_new),
+                              P(c_new), R, H, nl * H, P(planes), st)
                 rec.update(gates=gates, c_new=c_new)
                 h, c = h_new, c_new
                 zin = h_new
@@ -161,8 +190,11 @@ class _GcnStack(torch.autograd.Function):
             L = ctx.layers[i]
             dP = new(R, H)
             dhi = dhi_all[:, i * H:(i + 1) * H] if one_outer else new(R, H)
-            _hip.call("mmdfn_gcnii_layer_bwd_ld", P(dcur), P(L["gmask"]), P(convW[i]), P(dP), P(dhi), P(dh0), L["theta"],
-                      m["alpha"], R, H, lddo, acc_h0, dhi.stride(0), st)
+            img = _image("layer_bwd", R, convW[i])
+            if img is None or _hip.call("mmdfn_gcnii_layer_bwd_ld_img", P(dcur), P(L["gmask"]), P(convW[i]), P(dP), P(dhi), P(dh0),
+                                        L["theta"], m["alpha"], R, H, lddo, acc_h0, dhi.stride(0), P(img), st, allow=(-2,)) == -2:
+                _hip.call("mmdfn_gcnii_layer_bwd_ld", P(dcur), P(L["gmask"]), P(convW[i]), P(dP), P(dhi), P(dh0), L["theta"],
+                          m["alpha"], R, H, lddo, acc_h0, dhi.stride(0), st)
             acc_h0 = 1
             # dW_i = [hi | h0]^T dP: two row ranges of the (2H, H) parameter, the concatenated operand never exists
             wgrad(L["hi"], dP, convW[i], rows=(0, H))
@@ -175,9 +207,13 @@ class _GcnStack(torch.autograd.Function):
                 dG, dq = new(R, 4 * H), new(R, H)
                 dh_prev = new(R, H) if has_h else None
                 dc_prev = new(R, H) if has_h else None
-                _hip.call("mmdfn_lstm_gate_bwd", P(L["gates"]), P(L["c_prev"]), P(L["c_new"]), P(dz), P(dh_carry),
-                          P(dc_carry), P(w_ih), P(w_hh), P(dcur), P(dG), P(dc_prev), P(dq),
-                          P(dh_prev), R, H, 1 if has_h else 0, lddo, st)
+                img = _image("gate_bwd", R, w_ih, w_hh)       # (W_ih's column blocks come first: one image serves has_h = 0 too)
+                if img is None or _hip.call("mmdfn_lstm_gate_bwd_img", P(L["gates"]), P(L["c_prev"]), P(L["c_new"]), P(dz),
+                                            P(dh_carry), P(dc_carry), P(w_ih), P(w_hh), P(dcur), P(dG), P(dc_prev), P(dq),
+                                            P(dh_prev), R, H, 1 if has_h else 0, lddo, P(img), st, allow=(-2,)) == -2:
+                    _hip.call("mmdfn_lstm_gate_bwd", P(L["gates"]), P(L["c_prev"]), P(L["c_new"]), P(dz), P(dh_carry),
+                              P(dc_carry), P(w_ih), P(w_hh), P(dcur), P(dG), P(dc_prev), P(dq),
+                              P(dh_prev), R, H, 1 if has_h else 0, lddo, st)
                 wgrad(dG, L["q"], w_ih, [b_ih, b_hh])
                 if has_h:
                     wgrad(dG, L["h_prev"], w_hh)
@@ -189,8 +225,11 @@ class _GcnStack(torch.autograd.Function):
             # dA = [dhi_1 | .. | dhi_nl] [zin_1 | .. | zin_nl]^T on the tile / diagonal pattern: the tile array is written once
             dtiles, dcross = ops.tile_outer_raw(dhi_all, m["zin_all"], lay)
         dpre, dx = new(R, H), new(R, F)
-        _hip.call("mmdfn_gcn_input_bwd", P(dcur), P(m["m0"]), P(dh0), P(m["h0"]), P(W0), P(dxd), P(m["mx"]), P(dpre), P(dx), R,
-                  F, H, lddxd, m["mscale"], st)
+        img = _image("input_bwd", R, W0, F=F)
+        if img is None or _hip.call("mmdfn_gcn_input_bwd_img", P(dcur), P(m["m0"]), P(dh0), P(m["h0"]), P(W0), P(dxd), P(m["mx"]),
+                                    P(dpre), P(dx), R, F, H, lddxd, m["mscale"], P(img), st, allow=(-2,)) == -2:
+            _hip.call("mmdfn_gcn_input_bwd", P(dcur), P(m["m0"]), P(dh0), P(m["h0"]), P(W0), P(dxd), P(m["mx"]), P(dpre), P(dx), R,
+                      F, H, lddxd, m["mscale"], st)
         xd = m["xd"][:, :F] if m["use_residue"] else m["xd"]
         wgrad(dpre, xd, W0, [b0] if b0 is not None else [])
         pg = [None if p is None else inline.get(id(p)) for p in (W0, b0, w_ih, w_hh, b_ih, b_hh)]

@@ -90,7 +90,9 @@ class CapturedStep:
                 self.loss = step_fn()
                 tail(update=True)
         self._pinned = list(used)
-        self._planes = list(planes)
+        self._planes = [e for e in planes if e.image is None]
+        # ... and the GCN stack kernels' weight fragment images (ops_linear.stack_image): same registry, same re-check
+        self._images = [e for e in planes if e.image is not None]
         self._rng_per_replay = ops.flags_consumed(dev_index) - consumed0      # Philox counters one replay consumes
         torch.cuda.set_rng_state(rng_state, dev_index)
         ops.flag_state_restore(dev_index, flag_snap)
@@ -108,6 +110,7 @@ class CapturedStep:
         self.grads = {}
         self._pinned = []
         self._planes = []
+        self._images = []
         self._step_fn = None
         self.optimizer = None
         if graph is not None:
@@ -123,8 +126,8 @@ class CapturedStep:
                                    "materialisation / .to() / load_state_dict(assign=True)); capture again")
         if self._rng_per_replay:
             ops.flag_state_sync(self._dev_index)           # torch.manual_seed / a restored RNG state since the last draw
-        if self._planes:
-            ops.refresh_planes(self._planes)               # (host-side version check; a launch only after a weight update)
+        if self._planes or self._images:
+            ops.refresh_planes(self._planes + self._images)    # (host-side version check; a launch only after a weight update)
         if self.optimizer is not None:
             self.optimizer._push_hyper()                   # lr / weight decay changed since the last launch (a scheduler)
         self.graph.replay()

@@ -448,7 +448,7 @@ _PLANE_RECORDERS = []
 
 
 class _PlaneEntry:
-    __slots__ = ("w1", "w2", "mode", "N", "K", "n1", "buf", "epoch", "stamp", "__weakref__")
+    __slots__ = ("w1", "w2", "mode", "N", "K", "n1", "buf", "epoch", "stamp", "image", "__weakref__")
 
 
 def _plane_stamp(w1, w2):
@@ -471,6 +471,19 @@ def _cut_planes(entries):
     pa, ia = _hip.ptr_array, _hip.int_array
     live = [(e, _plane_params(e)) for e in entries]
     live = [(e, p[0], p[1]) for e, p in live if p is not None]
+    images = [t for t in live if t[0].image is not None]
+    live = [t for t in live if t[0].image is None]
+    for i in range(0, len(images), 16):
+        # fragment images of the GCN stack kernels (csrc/stack_images.hip): exact fp32, same registry, same stamps
+        chunk = images[i:i + 16]
+        _hip.call(
+            "mmdfn_cut_stack_images",
+            len(chunk), ia([e.image[0] for e, _, _ in chunk]), pa([w1 for _, w1, _ in chunk]), pa([w2 for _, _, w2 in chunk]),
+            ia([e.image[1] for e, _, _ in chunk]), ia([e.image[2] for e, _, _ in chunk]), ia([e.image[3] for e, _, _ in chunk]),
+            pa([e.buf for e, _, _ in chunk]), _hip.stream())
+        for e, w1, w2 in chunk:
+            e.epoch = _PLANE_EPOCH[0]
+            e.stamp = _plane_stamp(w1, w2)
     for i in range(0, len(live), 16):
         chunk = live[i:i + 16]
         _hip.call(
@@ -506,6 +519,7 @@ def weight_planes(w1, w2=None, transposed=False, mode=None):
         e = _PlaneEntry()
         e.w1, e.w2 = weakref.ref(w1), (None if w2 is None else weakref.ref(w2))
         e.mode = int(mode)
+        e.image = None
         if mode == 0:
             e.N, e.K, e.n1 = rows, cols, w1.shape[0]
         elif mode == 1:
@@ -517,6 +531,45 @@ def weight_planes(w1, w2=None, transposed=False, mode=None):
         nbytes = _hip.query("mmdfn_weight_planes_workspace", e.N, e.K)
         if nbytes <= 0:
             raise _hip.HipLibraryError("mmdfn_weight_planes_workspace refused N=%d K=%d" % (e.N, e.K))
+        e.buf = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
+        e.epoch, e.stamp = -1, None
+        _PLANES[key] = e
+    if not _plane_fresh(e, (w1, w2)):
+        _cut_planes([e])
+    for rec in _PLANE_RECORDERS:
+        if e not in rec:
+            rec.append(e)
+    return e
+
+
+STACK_IMAGE_KINDS = dict(input_fwd=0, input_bwd=1, layer_bwd=2, gate_fwd=3, gate_bwd=4)     # csrc/stack_image_map.h
+
+
+def stack_image_supported(*weights):
+    return all(w is None or (w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous()) for w in weights)
+
+
+def stack_image(kind, w1, w2=None, F=0):
+    """The fragment-image entry of a GCN stack kernel's weight slice (``kind``: a key of STACK_IMAGE_KINDS; ``w2``: W_hh of the
+    gate kinds, None for the layer without a previous state; ``F``: the input kinds' feature width).  An entry of the piece-plane
+    registry: same stamps, re-cut by refresh_planes() / in front of CapturedStep.replay() / after invalidate_planes(), cut now
+    if it is new or stale.  Returns None for a shape the image does not cover."""
+    import weakref
+    k = STACK_IMAGE_KINDS[kind]
+    has_h = 0 if w2 is None else 1
+    H = w1.shape[1] if k >= 2 else w1.shape[0]
+    key = (id(w1), 0 if w2 is None else id(w2), 100 + k)
+    e = _PLANES.get(key)
+    if e is not None and (e.w1() is not w1 or (w2 is not None and e.w2() is not w2) or e.image != (k, H, int(F), has_h)):
+        e = None                                   # an id recycled by another tensor
+    if e is None:
+        nbytes = _hip.query("mmdfn_stack_images_workspace", k, H, int(F), has_h)
+        if nbytes <= 0 or not stack_image_supported(w1, w2):
+            return None
+        e = _PlaneEntry()
+        e.w1, e.w2 = weakref.ref(w1), (None if w2 is None else weakref.ref(w2))
+        e.mode, e.N, e.K, e.n1 = 100 + k, 0, 0, 0
+        e.image = (k, H, int(F), has_h)
         e.buf = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
         e.epoch, e.stamp = -1, None
         _PLANES[key] = e
