@@ -818,6 +818,44 @@ int mmdfn_focal_loss_fwd_ignore(const float* logp, const int64_t* target, const 
 int mmdfn_focal_loss_bwd_ignore(const float* coef, const int64_t* target, const float* dloss, const float* scale,
                                 float* dlogp, int64_t N, int C, int64_t ignore_index, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K11  speaker / modality embeddings of the graph input (MM_GCN.forward,
+ *      model_mm.py:78-93) on the (M, N, D) modality-major stack, M <= 3
+ * ---------------------------------------------------------------------------
+ * modal_rows: HOST array of M ints, the row of every slot in the (3, D) modality table (a 0, v 1, l 2); l_slot: the slot of
+ * 'l', -1 when absent (row 2 must sit in that slot and nowhere else).  speaker (S, D) / modal (3, D): NULL = not added.
+ *   s_n = first maximum of qmask[flat_idx[n], 0..P)   (qmask: (LB, P) fp32, flat_idx: (N,) int64 pad-strip rows t * B + b; an
+ *         index outside [0, LB) gives speaker 0), written to spk[n] (int32) when the speaker part runs (speaker and 'l' present)
+ *   Y[l_slot] = (X[l_slot] + speaker[s_n]) + modal[2],   Y[m] = X[m] + modal[modal_rows[m]]     (plain fp32 adds)
+ * Returns -1 on bad arguments (P > S among them), -2 having launched nothing when D % 4 != 0, a pointer is not 16-byte aligned
+ * or S > mmdfn_graph_embed_max_speakers() (callers take another path).  One launch, grid from (M, N, D) only.
+ * Backward (dX is dY itself): dspeaker[s] = sum_{n: spk[n] = s} dY[l_slot, n, :]  (all S rows written; no utterance: 0),
+ * dmodal[modal_rows[m]] = sum_n dY[m, n, :]  (all 3 rows written; absent modalities: 0); either may be NULL.  One launch, no
+ * atomics, no workspace, fixed summation order: rows n = g, g + R, g + 2R, ... per row group g < R = mmdfn_graph_embed_rows(),
+ * then the groups in order.  Same -1 / -2 rules.  mmdfn_graph_embed_threads(): 16-byte lanes per forward workgroup. */
+int mmdfn_graph_embed_rows(void);
+int mmdfn_graph_embed_threads(void);
+int mmdfn_graph_embed_max_speakers(void);
+int mmdfn_graph_embed_fwd(const float* X, const float* qmask, const int64_t* flat_idx, const float* speaker, const float* modal,
+                          const int32_t* modal_rows, int l_slot, float* Y, int32_t* spk, int M, int N, int D, int P, int S,
+                          int64_t LB, void* stream);
+int mmdfn_graph_embed_bwd(const float* dY, const int32_t* spk, float* dspeaker, float* dmodal, const int32_t* modal_rows,
+                          int l_slot, int M, int N, int D, int S, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K12  NLLLoss (torch.nn.NLLLoss(weight, ignore_index, reduction 'mean' / 'sum'), run_train_erc.py:509)
+ * ---------------------------------------------------------------------------
+ * loss = sum_{t_i != ignore} w[t_i] (-logp[i, t_i]) / sum_{t_i != ignore} w[t_i]   (mean != 0; mean == 0: no division; weight
+ * NULL: 1).  One workgroup of mmdfn_nll_loss_threads() threads, fixed-order reduction in float64.  coef[i] = -w[t_i] (0 for
+ * an ignored row), scale_out[0] = 1 / sum of the weights (1 without mean).  Every row ignored: loss 0, zero gradients (torch:
+ * NaN); a label outside [0, C) that is not ignore_index: NaN loss, NaN gradient row.  weight must hold C entries.
+ * Backward: dlogp[i, c] = (c == t_i) coef[i] scale[0] dloss[0]. */
+int mmdfn_nll_loss_threads(void);
+int mmdfn_nll_loss_fwd(const float* logp, const int64_t* target, const float* weight, float* loss, float* coef,
+                       float* scale_out, int64_t N, int C, int mean, int64_t ignore_index, void* stream);
+int mmdfn_nll_loss_bwd(const float* coef, const int64_t* target, const float* dloss, const float* scale, float* dlogp,
+                       int64_t N, int C, int64_t ignore_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,39 +26,9 @@ from . import gru as fused_gru
 from . import ops
 from .fusion import LMF, MFN, MMGatedAttention
 from .graph_conv import GCNII
-from .layout import IndexScope, PinnedLRU
+# (the pad-strip index helpers live in layout.py: MM_GCN.forward_stacked builds the same index for the speaker embedding)
+from .layout import _FLAT_CACHE, flat_index as _flat_index, flat_inverse as _flat_inverse  # noqa: F401
 from .mm_gcn import MM_GCN
-
-_FLAT_CACHE = PinnedLRU(64)
-
-
-def _flat_index(lengths, L, B, device):
-    """Row ids t*B+b of the (L*B) padded grid in dialogue-major order (simple_batch_graphify)."""
-    def rows(lens):
-        lens = np.asarray([int(n) for n in lens], dtype=np.int64)
-        start = np.cumsum(lens) - lens
-        t = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(start, lens)             # position inside the dialogue
-        return t * B + np.repeat(np.arange(lens.size, dtype=np.int64), lens)
-    scope = IndexScope.current()
-    if scope is not None:             # a captured step replayed for other length lists owns (and rewrites) its index tensors
-        return scope.tensor(("flat", L, B, str(device)), lengths, rows, device)
-    return _FLAT_CACHE.get((tuple(lengths), L, B, str(device)), lambda: torch.from_numpy(rows(lengths)).to(device))
-
-
-def _flat_inverse(lengths, L, B, device):
-    """(L * B,) int64: the row of padded-grid position t*B+b in the dialogue-major stripped order, -1 for padding (the inverse of
-    _flat_index; the combine stage's backward writes its outputs by destination with it)."""
-    def rows(lens):
-        lens = np.asarray([int(n) for n in lens], dtype=np.int64)
-        start = np.cumsum(lens) - lens
-        t = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(start, lens)
-        inv = np.full(L * B, -1, dtype=np.int64)
-        inv[t * B + np.repeat(np.arange(lens.size, dtype=np.int64), lens)] = np.arange(int(lens.sum()), dtype=np.int64)
-        return inv
-    scope = IndexScope.current()
-    if scope is not None:
-        return scope.tensor(("flat_inv", L, B, str(device)), lengths, rows, device)
-    return _FLAT_CACHE.get((tuple(lengths), L, B, str(device), "inv"), lambda: torch.from_numpy(rows(lengths)).to(device))
 
 
 class _Scalar(nn.Module):
@@ -331,11 +301,8 @@ class DialogueGNNModel(nn.Module):
         # without the memory-fusion stage the head reads the (M, N, 300) graph output in place (stacked_out): the
         # cat([a, v, l], -1) of model_mm.py:113-117 and its backward are never materialised
         stacked = self.att_type != 'mfn'
-        if self.use_speaker or self.use_modal:
-            by = dict(zip(self.present, (feats[i] for i in range(len(self.present)))))
-            fused = self.graph_model(by.get('a', []), by.get('v', []), by.get('l', []), seq_lengths, qmask, test_label, stacked)
-        else:
-            fused = self.graph_model.forward_stacked(feats, seq_lengths, qmask, test_label, stacked)
+        # (use_speaker / use_modal: one launch on the stack inside forward_stacked, its pad-strip index is the encoder's)
+        fused = self.graph_model.forward_stacked(feats, seq_lengths, qmask, test_label, stacked)
         if test_label:
             # model.py:1297-1301: the fused (N, 900) graph output of the inference pass, in the reference's column order
             import os

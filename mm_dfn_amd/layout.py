@@ -151,6 +151,38 @@ class IndexScope:
         self.lengths = lengths
 
 
+_FLAT_CACHE = PinnedLRU(64)
+
+
+def flat_index(lengths, L, B, device):
+    """Row ids t*B+b of the (L*B) padded grid in dialogue-major order (simple_batch_graphify)."""
+    def rows(lens):
+        lens = np.asarray([int(n) for n in lens], dtype=np.int64)
+        start = np.cumsum(lens) - lens
+        t = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(start, lens)             # position inside the dialogue
+        return t * B + np.repeat(np.arange(lens.size, dtype=np.int64), lens)
+    scope = IndexScope.current()
+    if scope is not None:             # a captured step replayed for other length lists owns (and rewrites) its index tensors
+        return scope.tensor(("flat", L, B, str(device)), lengths, rows, device)
+    return _FLAT_CACHE.get((tuple(lengths), L, B, str(device)), lambda: torch.from_numpy(rows(lengths)).to(device))
+
+
+def flat_inverse(lengths, L, B, device):
+    """(L * B,) int64: the row of padded-grid position t*B+b in the dialogue-major stripped order, -1 for padding (the inverse of
+    flat_index; the combine stage's backward writes its outputs by destination with it)."""
+    def rows(lens):
+        lens = np.asarray([int(n) for n in lens], dtype=np.int64)
+        start = np.cumsum(lens) - lens
+        t = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(start, lens)
+        inv = np.full(L * B, -1, dtype=np.int64)
+        inv[t * B + np.repeat(np.arange(lens.size, dtype=np.int64), lens)] = np.arange(int(lens.sum()), dtype=np.int64)
+        return inv
+    scope = IndexScope.current()
+    if scope is not None:
+        return scope.tensor(("flat_inv", L, B, str(device)), lengths, rows, device)
+    return _FLAT_CACHE.get((tuple(lengths), L, B, str(device), "inv"), lambda: torch.from_numpy(rows(lengths)).to(device))
+
+
 def pair_list(M):
     return [(m, n) for m in range(M) for n in range(m + 1, M)]
 

@@ -1,4 +1,5 @@
-"""FocalLoss (reference loss.py:5-34): -(1-pt)^gamma * alpha_t * log(pt), pt detached."""
+"""FocalLoss (reference loss.py:5-34): -(1-pt)^gamma * alpha_t * log(pt), pt detached; NLLLoss: the training script's other
+objective, torch.nn.NLLLoss(class weights) (run_train_erc.py:509)."""
 import torch
 import torch.nn as nn
 
@@ -130,3 +131,77 @@ class FocalLoss(nn.Module):
         if self.ignore_index is not None and loss.numel() == 0:
             return loss.sum()            # every row left out: 0 with zero gradients, as the device form (not the NaN of an empty mean)
         return loss.mean() if self.size_average else loss.sum()
+
+
+def nll_block_rows():
+    """Rows one pass of the forward launch's single workgroup covers (csrc/nll_loss.hip)."""
+    from . import _hip
+    return int(_hip.query("mmdfn_nll_loss_threads"))
+
+
+class _NLLLossHip(torch.autograd.Function):
+    """One launch each way (csrc/nll_loss.hip): the forward writes the per-row coefficient -w[t] and 1 / (sum of the weights
+    that count) on the device, so a captured step serves batches with different numbers of rows that count."""
+
+    @staticmethod
+    def forward(ctx, logp, target, weight, mean, ignore_index):
+        from . import _hip
+        logp = logp.contiguous()
+        target = target.reshape(-1).contiguous()
+        N, C = logp.shape
+        loss = torch.empty((), dtype=torch.float32, device=logp.device)
+        scale = torch.empty(1, dtype=torch.float32, device=logp.device)
+        coef = torch.empty(N, dtype=torch.float32, device=logp.device)
+        _hip.call("mmdfn_nll_loss_fwd", _hip.ptr(logp), _hip.ptr(target), _hip.ptr(weight), _hip.ptr(loss), _hip.ptr(coef),
+                  _hip.ptr(scale), N, C, 1 if mean else 0, int(ignore_index), _hip.stream())
+        ctx.save_for_backward(coef, target, scale)
+        ctx.C, ctx.ignore = C, int(ignore_index)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import _hip
+        coef, target, scale = ctx.saved_tensors
+        N = coef.shape[0]
+        dlogp = torch.empty(N, ctx.C, dtype=torch.float32, device=coef.device)
+        dl = dloss.contiguous().to(torch.float32)
+        _hip.call("mmdfn_nll_loss_bwd", _hip.ptr(coef), _hip.ptr(target), _hip.ptr(dl), _hip.ptr(scale), _hip.ptr(dlogp), N,
+                  ctx.C, ctx.ignore, _hip.stream())
+        return dlogp, None, None, None, None
+
+
+class NLLLoss(nn.Module):
+    """``torch.nn.NLLLoss(weight, ignore_index, reduction)`` with the arguments the reference's training script uses
+    (run_train_erc.py:509, --loss NLLLoss [--class_weight]) on (N, C) log-probabilities:
+    ``sum_i w[t_i] (-input[i, t_i]) / sum_i w[t_i]`` over the rows whose label is not ``ignore_index`` ('mean'; 'sum' does not
+    divide).  NOT FocalLoss(gamma=0, alpha=w): that one divides by the number of rows.
+
+    Device tensors run one fused launch each way.  Where it differs from torch, as FocalLoss's ignore_index form does: with
+    every row ignored the loss is 0 with zero gradients (torch: NaN), and a label outside [0, C) that is not ``ignore_index``
+    gives a NaN loss and NaN gradients (torch raises; a kernel cannot without a host synchronisation).  A weight table shorter
+    than C raises IndexError.  Host tensors go to ``torch.nn.functional.nll_loss`` unchanged."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction='mean'):
+        super().__init__()
+        if reduction == 'none':
+            raise NotImplementedError("NLLLoss: reduction='none' is not implemented (the training script reduces)")
+        if reduction not in ('mean', 'sum'):
+            raise ValueError("NLLLoss: reduction must be 'mean' or 'sum', got %r" % (reduction,))
+        if isinstance(weight, (list, tuple)):
+            weight = torch.tensor(weight, dtype=torch.float32)
+        self.weight = weight
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        weight = self.weight
+        if weight is not None and (weight.device != input.device or weight.dtype != input.dtype):
+            weight = self.weight = weight.to(device=input.device, dtype=input.dtype)
+        if input.is_cuda and input.dtype == torch.float32 and input.dim() == 2 and target.dtype == torch.int64:
+            if weight is not None and weight.numel() < input.shape[1]:
+                raise IndexError("NLLLoss: weight has %d entries for %d classes" % (weight.numel(), input.shape[1]))
+            if weight is not None:
+                weight = weight.contiguous()
+            return _NLLLossHip.apply(input, target, weight, self.reduction == 'mean', self.ignore_index)
+        import torch.nn.functional as F
+        return F.nll_loss(input, target, weight, ignore_index=self.ignore_index, reduction=self.reduction)

@@ -5,6 +5,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .graph_conv import GCNII_lyc
+from .layout import flat_index
 
 
 class MM_GCN(nn.Module):
@@ -91,12 +92,23 @@ class MM_GCN(nn.Module):
             raise NotImplementedError("forward_streams: speaker / modality embeddings exist for 'avl' graphs only")
         return self._graph(ops.build_adjacency(feats, dia_len, self.modal_weight), qmask, test_label, stacked_out)
 
-    def forward_stacked(self, feats, dia_len, qmask, test_label=False, stacked_out=False):
+    def forward_stacked(self, feats, dia_len, qmask, test_label=False, stacked_out=False, flat_idx=None):
         """Same as forward(a, v, l, ...) for features that are already one (M, N, D) stack in modality order (what the
         fused encoder epilogue writes): skips the unbind / re-stack round trip and its select-backward zero fills.
-        Not available with use_speaker / use_modal (they edit single modalities in place, model_mm.py:78-93)."""
-        if self.use_speaker or self.use_modal:
-            raise NotImplementedError("forward_stacked: use forward(a, v, l, ...) with use_speaker / use_modal")
-        if feats.dim() != 3 or feats.shape[0] != len(''.join(self.modals)) or feats.shape[0] < 2:
+        use_speaker / use_modal (model_mm.py:78-93) are one launch on the stack (ops.graph_embeddings) that returns a NEW
+        stack -- the caller's tensor is not edited, unlike forward() -- and reads the speaker of every row from ``qmask``
+        (L, B, P) through ``flat_idx``, the (N,) pad-strip index t * B + b (built from qmask.shape and dia_len when not
+        given): nothing is sliced or synchronised on the host."""
+        modals = ''.join(self.modals)
+        if feats.dim() != 3 or feats.shape[0] != len(modals) or feats.shape[0] < 2:
             raise ValueError("forward_stacked expects a (len(modals), N, D) stack")
+        if self.use_speaker or self.use_modal:
+            present = [k for k in 'avl' if k in modals]
+            if len(present) != len(modals):
+                raise NotImplementedError("forward_stacked: speaker / modality embeddings exist for 'avl' graphs only")
+            speaker = self.speaker_embeddings.weight if self.use_speaker and 'l' in present else None
+            modal = self.modal_embeddings.weight if self.use_modal else None
+            if speaker is not None and flat_idx is None:
+                flat_idx = flat_index([int(x) for x in dia_len], int(qmask.shape[0]), int(qmask.shape[1]), feats.device)
+            feats = ops.graph_embeddings(feats, qmask, flat_idx, speaker, modal, present)
         return self._graph(ops.build_adjacency(feats, dia_len, self.modal_weight), qmask, test_label, stacked_out)

@@ -49,3 +49,6 @@ from .ops_flags import (  # noqa: F401
 from .ops_head import (  # noqa: F401
     _Head, _head_width, head_supported, head,
 )
+from .ops_embed import (  # noqa: F401
+    _GraphEmbeddings, graph_embeddings,
+)

@@ -93,8 +93,11 @@ class StepGraphCache:
         of the same (B, L) that its padding dialogue can fill (at most L utterances: up to ~L / g buckets above its own)
         instead of being captured in the middle of a pass (55-90 ms at cfg2 against a few percent more rows for that step);
         ``fallbacks`` counts them, ``precapture`` still captures every bucket it meets exactly.
-        Needs a mm_dfn_amd FocalLoss (its ignore_index form) and a model without use_speaker / use_modal (they slice by
-        dialogue length on the host); anything else falls back to exact signatures.
+        Needs a mm_dfn_amd FocalLoss (its ignore_index form) or a mm_dfn_amd NLLLoss (taken as it is when its ignore_index is
+        IGNORE, torch's default; otherwise a copy that ignores IGNORE steps the bucketed entries); any other loss object falls
+        back to exact signatures.  use_speaker / use_modal models are served too: their embeddings are added by one row-wise
+        launch that reads the speakers from qmask through the retargeted pad-strip index (ops.graph_embeddings), the padding
+        dialogue is speaker 0's monologue and adds exact zeros to the table gradients.
         ``optimizer``: a device-state FlatAdam (``capturable=True`` / ``max_grad_norm`` / ``skip_nonfinite``) captured into every
         TRAINING entry, exact and bucketed (graphs.CapturedStep(optimizer=...)); eval entries are captured without it.  The pass
         loop must then not step it again (train_or_eval_graph_model does not), and ``precapture`` replays with the update
@@ -114,10 +117,14 @@ class StepGraphCache:
         self._exact_buckets = False        # (precapture: every bucket it meets gets its own entry)
         self._loss_ign = None
         if self.bucket_rows:
-            from .loss import FocalLoss
+            from .loss import FocalLoss, NLLLoss
             if isinstance(loss_f, FocalLoss) and loss_f.ignore_index is None:
                 self._loss_ign = FocalLoss(gamma=loss_f.gamma, alpha=loss_f.alpha, size_average=loss_f.size_average,
                                            ignore_index=self.IGNORE)
+            elif isinstance(loss_f, NLLLoss):
+                # (torch's default ignore_index IS -100: the usual object is taken as it is)
+                self._loss_ign = loss_f if loss_f.ignore_index == self.IGNORE else NLLLoss(
+                    weight=loss_f.weight, ignore_index=self.IGNORE, reduction=loss_f.reduction)
 
     def _hand_over_grads(self, ent):
         """``p.grad`` = the gradient tensors the entry's graph writes (walking named_parameters() on every step cost the
@@ -130,10 +137,8 @@ class StepGraphCache:
             p.grad = g
 
     def _bucketable(self, inputs, lengths, test_label):
-        m = self.model
         L = int(inputs[0].shape[0])
-        return (self._loss_ign is not None and not test_label and not getattr(m, "use_speaker", False)
-                and not getattr(m, "use_modal", False) and self.bucket_rows <= L and all(t.is_cuda for t in inputs)
+        return (self._loss_ign is not None and not test_label and self.bucket_rows <= L and all(t.is_cuda for t in inputs)
                 and int(max(lengths)) == L)
 
     def _bucket_key(self, inputs, lengths, train_flag):
