@@ -856,6 +856,28 @@ int mmdfn_nll_loss_fwd(const float* logp, const int64_t* target, const float* we
 int mmdfn_nll_loss_bwd(const float* coef, const int64_t* target, const float* dloss, const float* scale, float* dlogp,
                        int64_t N, int C, int64_t ignore_index, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Fold-back of the encoder input projections (ABI 23, additive; csrc/fold_back.hip)
+ * ---------------------------------------------------------------------------
+ * X_m = u_m W_m^T + b_m feeds a GRU's first-layer input contraction with nothing in between, so both layers' weight gradients
+ * follow from M = dG^T u_m (n x D) and c = colsum(dG) (n), which the weight-gradient batch leaves.  One TERM = one (direction
+ * half of W_ih, modality) pair; per term
+ *   dwih (n x H)  (+)= M wm^T + c bm^T        (wm: H x D, bm: H or NULL)
+ *   dwm  (H x D)  (+)= wih^T M                (wih: n x H)
+ *   dbm  (H)      (+)= wih^T c
+ * Terms that name the same dwih (same n) or the same dwm / dbm (same D) are summed in term order (fp32 chains of 32 products,
+ * their sums in float64) and rounded once behind the existing gradient (acc_wih[t] / acc_wm[t] != 0: accumulate, else write; taken from an output's first term).
+ * dwih[t] / dwm[t] / dbm[t] may be NULL (that product is not wanted).  1 <= nterm <= 16; D, H multiples of 4 (n: any), at most 32
+ * distinct outputs: otherwise -2; a missing operand -1.  No float atomics: bit-reproducible.
+ * workspace: mmdfn_fold_back_workspace(...) floats, 8-byte aligned; tickets: mmdfn_fold_back_tickets() int32, ZERO before the
+ * first launch that uses them -- every launch leaves them zero again (they may be shared by launches of one stream). */
+int mmdfn_fold_back_tickets(void);
+int64_t mmdfn_fold_back_workspace(int nterm, float* const* dwm, const int* n, const int* D, int H);
+int mmdfn_fold_back(int nterm, const float* const* M, const float* const* c, const float* const* wih,
+                    const float* const* wm, const float* const* bm, float* const* dwih, float* const* dwm,
+                    float* const* dbm, const int* n, const int* D, int H, const int* acc_wih, const int* acc_wm,
+                    float* workspace, int32_t* tickets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

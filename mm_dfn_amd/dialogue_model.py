@@ -245,8 +245,16 @@ class DialogueGNNModel(nn.Module):
                     cw, cb, _ = fused_gru._layer_params(gru, 0)
                     ridx[m] = len(riders)
                     riders.append((act.index(m), cw[0], cw[1], cb[0], cb[1], fused_gru._stacked_view(*cw)))
+            # a modality whose raw features need no gradient and are no wider than its projection names its source: the
+            # node's backward then derives linear_m's and the input contractions' weight gradients from dG^T u_m and
+            # launches no input-gradient product for it (ops_party.FOLD_BACK decides there, pass by pass: only inside a
+            # wgrad_batch() scope, only for unhooked leaf parameters; X_m W_ih^T has nothing between the two layers)
+            sources = [(raw[m], lin[m].weight, lin[m].bias)
+                       if (not raw[m].requires_grad and raw[m].shape[-1] % 4 == 0 and raw[m].shape[-1] <= X[m].shape[-1]
+                           and lin[m].weight.is_leaf) else None for m in act]
             gi_p, rank, *rest = ops.project_gather([X[m] for m in act], qmask, w_ih[0], w_ih[1], b_ih[0], b_ih[1],
-                                                   fused_gru._stacked_view(*w_ih), fused_gru._stacked_view(*b_ih), riders=riders)
+                                                   fused_gru._stacked_view(*w_ih), fused_gru._stacked_view(*b_ih), riders=riders,
+                                                   sources=sources if any(s is not None for s in sources) else None)
             passed, rode = rest[:len(act)], rest[len(act):]
             X.update(zip(act, passed))          # the gathered modalities come back as identities (one consumer each)
             if truncate:

@@ -284,6 +284,7 @@ class _LinearGroup(torch.autograd.Function):
         ctx.has_bias = [b is not None for b in bs]
         ctx.param_refs = list(zip(ws, bs))
         ctx.save_for_backward(*saved)
+        ctx.set_materialize_grads(False)        # an output nobody differentiates arrives as None, not as a zero fill
         return tuple(ys)
 
     @staticmethod
@@ -292,7 +293,13 @@ class _LinearGroup(torch.autograd.Function):
         dxs, wg, dy2s = [], [], []
         for g in range(n):
             x2, w, y = sv[3 * g], sv[3 * g + 1], sv[3 * g + 2]
-            dy2 = dys[g].reshape(-1, w.shape[0]) if dys[g] is not None else torch.zeros(x2.shape[0], w.shape[0], dtype=x2.dtype, device=x2.device)
+            if dys[g] is None:
+                # no gradient reached this output (its consumer derives this layer's weight gradients itself:
+                # ops_party.FOLD_BACK): nothing is contracted or queued for it
+                dy2s.append(None)
+                wg.append((None, None))
+                continue
+            dy2 = dys[g].reshape(-1, w.shape[0])
             if ctx.act:
                 dy2 = dy2 * (y > 0).to(dy2.dtype)
             dy2 = dy2.contiguous()
@@ -301,17 +308,17 @@ class _LinearGroup(torch.autograd.Function):
         if ctx.force:
             # input gradients dX_g = dY_g . W_g of the whole group in one launch: the weight is read as stored ((N, K) = the
             # K-major form of the product over N)
-            need = [g for g in range(n) if ctx.needs_input_grad[2 + g]]
+            need = [g for g in range(n) if ctx.needs_input_grad[2 + g] and dy2s[g] is not None]
             outs = linear_group_raw([_dx_problem(dy2s[g], weight_operand(sv[3 * g + 1])) for g in need]) if need else []
             dxs = [None] * n
             for g, o in zip(need, outs):
                 K = sv[3 * g + 1].shape[1]
-                dxs[g] = o[:, :K].reshape(*dys[g].shape[:-1], K) if dys[g] is not None else o[:, :K]
+                dxs[g] = o[:, :K].reshape(*dys[g].shape[:-1], K)
         else:
             for g in range(n):
                 w = sv[3 * g + 1]
                 dxs.append(_linear_dx(dy2s[g], weight_operand(w))[:, :w.shape[1]].reshape(*dys[g].shape[:-1], w.shape[1])
-                           if ctx.needs_input_grad[2 + g] else None)
+                           if ctx.needs_input_grad[2 + g] and dy2s[g] is not None else None)
         return (None, None) + tuple(dxs) + tuple(r[0] for r in wg) + tuple(r[1] for r in wg)
 
 

@@ -8,7 +8,8 @@ import torch
 from . import _hip
 from . import ops_linear
 from .ops_linear import _wgrad, linear_group_raw
-from .ops_wgrad import _WGQ, _queueable, _wgrad_inline, colsum, flush_queued_wgrads, queue_wgrad, slab_reduce_queueable
+from .ops_wgrad import (_WGQ, _queueable, _wgrad_inline, colsum, flush_queued_wgrads, fold_back_queueable, queue_fold_back,
+                        queue_wgrad, slab_reduce_queueable)
 
 
 class _PartyGather(torch.autograd.Function):
@@ -110,6 +111,11 @@ PARTY_ORDERED_STORE = __import__("os").environ.get("MMDFN_PARTY_ORDERED_STORE", 
 # _ProjectGather.backward: a rider's input gradient as second K segment of its source modality's problem ("0": the accumulating
 # launch behind it; A/B aid)
 RIDER_DX_SEGMENT = __import__("os").environ.get("MMDFN_RIDER_DX_SEGMENT", "1") != "0"
+# _ProjectGather.backward: for a modality whose source (u_m, W_m, b_m) the caller named, no input-gradient product -- the weight
+# gradients of the modality projection AND of the input contractions follow from dG^T u_m (ops_wgrad.queue_fold_back; "0": the
+# input-gradient launch and dG^T X_m as before; A/B aid)
+FOLD_BACK = __import__("os").environ.get("MMDFN_FOLD_BACK", "1") != "0"
+FOLD_BACK_TICKETS = 2048        # mmdfn_fold_back_tickets()
 
 
 class _ProjectGather(torch.autograd.Function):
@@ -122,7 +128,9 @@ class _ProjectGather(torch.autograd.Function):
     with X_m' identities of the inputs (see _PartyGather)."""
 
     @staticmethod
-    def forward(ctx, qmask, w1, w2, b1, b2, wcat, bcat, riders, *rest):
+    def forward(ctx, qmask, w1, w2, b1, b2, wcat, bcat, riders, sources, *rest):
+        # sources: None or, per gathered input, None / (u_m (L, B, D), W_m, b_m-or-None) with X_m = u_m W_m^T + b_m and u_m
+        # needing no gradient: the backward pass may then skip X_m's input-gradient product (FOLD_BACK)
         # riders: [(index into Xs, has_wcat), ...]; rest = 5 tensors per rider (w1, w2, b1, b2, wcat-or-None), then Xs.
         # A rider is ANOTHER projection of one of the gathered inputs that does not depend on this node's result (the context
         # GRU's first-layer input contraction of the same utterance rows, model.py:1132): it rides in the grouped launch of the
@@ -176,6 +184,7 @@ class _ProjectGather(torch.autograd.Function):
         ctx.dims = (L, B, P, H, Mn, n1, N)
         ctx.refs = (w1, w2, b1, b2)
         ctx.riders = [(src, tuple(pr[:4])) for (src, _), pr in zip(riders, rprm)]
+        ctx.sources = list(sources) if sources is not None else [None] * Mn
         ctx.save_for_backward(rank, w1c, w2c, wcat, *[pr[4] for pr in rprm], *[pr[0] for pr in rprm], *[pr[1] for pr in rprm], *mods)
         ctx.mark_non_differentiable(rank)
         ctx.set_materialize_grads(False)
@@ -215,7 +224,9 @@ class _ProjectGather(torch.autograd.Function):
             db1, db2 = db[:n1], db[n1:]
         # input gradients: dX_m = dG_m [W1; W2] (+ the gradient that reached X_m's alias), one grouped launch
         dXs = [None] * Mn
-        need = [m for m in range(Mn) if ctx.needs_input_grad[8 + 5 * nr + m]]
+        xgrad = 9 + 5 * nr                      # position of X_0 among the inputs
+        fold = _fold_plan(ctx, N, n1, H, dride) if FOLD_BACK and any(s is not None for s in ctx.sources) else {}
+        need = [m for m in range(Mn) if ctx.needs_input_grad[xgrad + m] and m not in fold]
         absorbed, rdy2 = set(), {}              # riders whose input gradient the grouped launch contracted; their dY rows
         if need:
             # dX_m = dG_m [W1; W2] + (the gradient that reached X_m's passthrough alias), out of place: the incoming gradient is
@@ -271,6 +282,8 @@ class _ProjectGather(torch.autograd.Function):
                 dXs[m] = o.view(L, B, H)
         else:
             dXs = [d for d in dpass] + [None] * (Mn - len(dpass))
+        for m in fold:                          # only what reached the passthrough alias (the combine stage's addend)
+            dXs[m] = dpass[m] if m < len(dpass) else None
         # riders: their input gradient is added onto the source modality's (the second K segment of the launch above, or a
         # second launch: two workgroups of one launch may not write the same rows), their weight / bias gradients are queued
         # like any projection's
@@ -282,7 +295,13 @@ class _ProjectGather(torch.autograd.Function):
                 continue
             dy2 = rdy2[i] if i in rdy2 else dyr.reshape(L * B, -1).contiguous()
             rn1 = rp1.shape[0]
-            if ctx.needs_input_grad[8 + 5 * nr + src] and i not in absorbed:
+            if src in fold:
+                u2, Wm, bm = fold[src]
+                queue_fold_back(dy2[:, :rn1], u2, rw1c[i].contiguous(), rp1, Wm, bm, bias=rb1)
+                queue_fold_back(dy2[:, rn1:], u2, rw2c[i].contiguous(), rp2, Wm, bm, bias=rb2)
+                rgrads += [None, None, None, None, None]
+                continue
+            if ctx.needs_input_grad[xgrad + src] and i not in absorbed:
                 if dXs[src] is None:
                     dXs[src] = torch.zeros(L, B, H, dtype=torch.float32, device=dev)
                 tgt = dXs[src].view(L * B, H)
@@ -301,6 +320,11 @@ class _ProjectGather(torch.autograd.Function):
             x2 = [m.view(L * B, H) for m in mods]
             if _queueable(p1, [], n1, H) and _queueable(p2, [], N - n1, H):
                 for m in range(Mn):
+                    if m in fold:
+                        u2, Wm, bm = fold[m]
+                        queue_fold_back(dG[m][:, :n1], u2, w1, p1, Wm, bm)
+                        queue_fold_back(dG[m][:, n1:], u2, w2, p2, Wm, bm)
+                        continue
                     queue_wgrad(dG[m][:, :n1], x2[m], p1)
                     queue_wgrad(dG[m][:, n1:], x2[m], p2)
             else:
@@ -309,19 +333,57 @@ class _ProjectGather(torch.autograd.Function):
                     b, _ = _wgrad_inline(dG[m][:, n1:], x2[m], False)
                     dw1 = a if dw1 is None else dw1 + a
                     dw2 = b if dw2 is None else dw2 + b
-        return (None, dw1, dw2, db1, db2, None, None, None) + tuple(rgrads) + tuple(dXs)
+        return (None, dw1, dw2, db1, db2, None, None, None, None) + tuple(rgrads) + tuple(dXs)
 
 
-def project_gather(Xs, qmask, w1, w2, b1, b2, wcat=None, bcat=None, riders=()):
+def _fold_plan(ctx, N, n1, H, dride):
+    """{gathered input m: (u_m as (L*B, D), W_m, b_m)} for the sourced inputs whose weight gradients this backward pass derives
+    from dG^T u_m (see FOLD_BACK): inside a wgrad_batch() scope, every parameter involved an unhooked leaf that wants its
+    gradient, at most one rider per source, widths the fold-back kernel takes.  Anything else: today's launches."""
+    p1, p2, _b1, _b2 = ctx.refs
+    if not (ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _queueable(p1, [], n1, H) and _queueable(p2, [], N - n1, H)
+            and n1 % 4 == 0):
+        return {}
+    plan = {}
+    for m, s in enumerate(ctx.sources):
+        if s is None:
+            continue
+        u, Wm, bm = s
+        D = u.shape[-1]
+        riders = [i for i, (src, _prm) in enumerate(ctx.riders) if src == m]
+        if not ctx.needs_input_grad[9 + 5 * len(ctx.riders) + m]:
+            continue                            # X_m is not part of the graph: W_m and b_m receive nothing through it
+        # (the fold-back launch's ticket words: 8 terms per launch, one ticket per 32 x 32 tile of dW_m / db_m)
+        if 8 * ((H + 31) // 32) * ((D + 32) // 32) > FOLD_BACK_TICKETS:
+            continue
+        # (D <= H: the contractions that remain are no longer than the ones they replace; a wider rule needs a measurement)
+        ok = (not u.requires_grad and D % 4 == 0 and D <= H and tuple(Wm.shape) == (H, D) and fold_back_queueable([Wm, bm])
+              and Wm.requires_grad and (bm is None or bm.requires_grad) and len(riders) <= 1)
+        for i in riders:
+            rp1, rp2, rb1, rb2 = ctx.riders[i][1]
+            live = i < len(dride) and dride[i] is not None
+            ok = ok and (not live or (fold_back_queueable([rp1, rp2, rb1, rb2]) and rp1.shape[0] % 4 == 0 and rp2.shape[0] % 4 == 0
+                                      and all(rb is None or rb.grad is None or rb.grad.is_contiguous() for rb in (rb1, rb2))))
+        if ok:
+            plan[m] = (u.reshape(-1, D), Wm, bm)
+    return plan
+
+
+def project_gather(Xs, qmask, w1, w2, b1, b2, wcat=None, bcat=None, riders=(), sources=None):
     """(gi_p, rank, X_0', .., [rider outputs]): see _ProjectGather.  ``wcat`` / ``bcat``: optional stacked views of [w1; w2] /
     [b1; b2] (no gradient flows through them; without wcat the input gradient takes two launches per modality, without bcat the
     bias is concatenated per call).  ``riders``: [(index into Xs, w1, w2, b1, b2, wcat-or-None), ...] -- further projections
-    X_index [w1; w2]^T + [b1; b2] computed in the same grouped launch, returned behind the identities as (L, B, .) tensors."""
+    X_index [w1; w2]^T + [b1; b2] computed in the same grouped launch, returned behind the identities as (L, B, .) tensors.
+    ``sources``: per gathered input None or (u_m, W_m, b_m) with X_m = u_m W_m^T + b_m computed by the caller and u_m needing no
+    gradient -- the backward pass may then derive W_m's, b_m's and the input contractions' weight gradients from dG^T u_m and
+    launch no input-gradient product for X_m (FOLD_BACK, _fold_plan); without it the node behaves as before."""
     if w1.shape[1] % 4 or (w1.shape[0] + w2.shape[0]) % 4:
         raise ValueError("project_gather: widths must be multiples of 4")
     meta = [(int(r[0]), r[5] is not None) for r in riders]
     flat = [t for r in riders for t in r[1:6]]
-    return _ProjectGather.apply(qmask, w1, w2, b1, b2, wcat, bcat, meta, *flat, *Xs)
+    if sources is not None and len(sources) != len(Xs):
+        raise ValueError("project_gather: one source (or None) per gathered input")
+    return _ProjectGather.apply(qmask, w1, w2, b1, b2, wcat, bcat, meta, sources, *flat, *Xs)
 
 
 class _PartyCombine(torch.autograd.Function):

@@ -133,6 +133,7 @@ class wgrad_batch:
             _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False        # stale entries of a backward that raised
         if _WGQ["scope"] == 0:
             drop_grad_addends()                                             # (same: its callback never ran)
+            del _FOLD[:]
             _WGQ["riders"], _WGQ["rider_keep"], _WGQ["rider_held"] = _hip.riders_context(), None, []
         _WGQ["scope"] += 1
         return self
@@ -144,9 +145,11 @@ class wgrad_batch:
                 if _WGQ["outs"] or _WGQ["ext"]:
                     flush_queued_wgrads()                  # a backward driven without the engine callback
                 _drain_riders()
+                _run_fold_back()
             else:
                 _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False    # the callback never ran: drop the half-built batch
                 drop_grad_addends()
+                del _FOLD[:]
                 _drain_riders(discard=True)
             _WGQ["riders"] = None
             _join_side()
@@ -221,6 +224,104 @@ def queue_slab_reduce(part, colpart, splits, M, N, weight=None, biases=()):
     if not _WGQ["armed"]:
         _WGQ["armed"] = True
         torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Fold-back of the encoder input projections (csrc/fold_back.hip).  Where X_m = u_m W_m^T + b_m feeds a GRU's
+# first-layer input contraction directly, the node of that contraction queues M = dG^T u_m and c = colsum(dG) into WORKSPACE
+# stand-ins instead of dG^T X_m and launches no dX product; one grouped launch behind the end-of-backward reduction derives
+# dW_ih, dW_m and db_m from them and writes (or accumulates into) the parameters' .grad.
+# ---------------------------------------------------------------------------------------------------
+_FOLD = []              # terms registered by the running backward pass, in registration order
+_FOLD_TICKETS = {}      # device -> the fold-back launch's zeroed ticket words (every launch leaves them zero)
+
+
+class _Workspace:
+    """Stand-in 'parameter' of queue_wgrad whose .grad is a plain tensor the batch allocates and fills."""
+    is_leaf = True
+    requires_grad = True
+
+    def __init__(self, shape, device):
+        self.shape = tuple(shape)
+        self.device = device
+        self.grad = None
+
+
+def fold_back_queueable(params):
+    """May the gradients of ``params`` (None entries ignored) be written by the fold-back launch?  Same rules as queue_wgrad."""
+    return _WGQ["scope"] > 0 and all(_leaf(p) and not _hooked(p) for p in params if p is not None)
+
+
+def queue_fold_back(A, u, w_ih, p_ih, W_m, b_m, bias=None):
+    """One fold-back term: with M = A^T u and c = colsum(A) (A (R, n): the pre-activation gradient of one direction half of a
+    first-layer input contraction in utterance order, u (R, D): the raw features behind it),
+      p_ih.grad += M W_m^T + c b_m^T,   W_m.grad += w_ih^T M,   b_m.grad += w_ih^T c
+    (w_ih (n, H): the half as the forward contracted it).  ``bias``: a leaf bias whose gradient IS c (a rider's b_ih half).
+    M and c ride in the end-of-backward batch; the fold-back launch follows its reduction."""
+    n, D = A.shape[1], u.shape[1]
+    Mh, ch = _Workspace((n, D), A.device), _Workspace((n,), A.device)
+    queue_wgrad(A, u, Mh, ([bias] if bias is not None else []) + [ch])
+    _FOLD.append(dict(M=Mh, c=ch, wih=w_ih, p=p_ih, wm=W_m, bm=b_m))
+
+
+def _fold_tickets(dev):
+    t = _FOLD_TICKETS.get(dev)
+    if t is None:
+        t = torch.zeros(int(_hip.query("mmdfn_fold_back_tickets")), dtype=torch.int32, device=dev)
+        if torch.cuda.is_current_stream_capturing():
+            return t            # (its fill is a node of this graph only: not kept for launches outside it)
+        _FOLD_TICKETS[dev] = t
+    return t
+
+
+def _run_fold_back():
+    """The fold-back launch of the terms registered by this backward pass (behind every reduction of the batch)."""
+    if not _FOLD:
+        return
+    terms = list(_FOLD)
+    del _FOLD[:]
+    dev = terms[0]["M"].grad.device
+    seen = {}
+
+    def target(p):
+        if p is None:
+            return None, 0
+        if id(p) not in seen:
+            if p.grad is None:
+                p.grad = torch.empty(tuple(p.shape), dtype=torch.float32, device=dev)
+                seen[id(p)] = 0
+            else:
+                if not p.grad.is_contiguous():
+                    p.grad = p.grad.contiguous()
+                seen[id(p)] = 1
+        return p.grad, seen[id(p)]
+
+    # one launch per <= 8 terms of one H (the entry point takes 16 terms and 32 outputs): a backward pass over several forward
+    # passes registers more; an output a later launch meets again is accumulated
+    groups = []
+    for H in sorted({int(t["wm"].shape[0]) for t in terms}):
+        same = [t for t in terms if int(t["wm"].shape[0]) == H]
+        groups += [(H, same[i:i + 8]) for i in range(0, len(same), 8)]
+    for H, grp in groups:
+        M = [t["M"].grad for t in grp]
+        c = [t["c"].grad for t in grp]
+        wih = [t["wih"].detach().contiguous() for t in grp]
+        wm = [t["wm"].detach().contiguous() for t in grp]
+        bm = [None if t["bm"] is None else t["bm"].detach().contiguous() for t in grp]
+        tw, tm, tb = [target(t["p"]) for t in grp], [target(t["wm"]) for t in grp], [target(t["bm"]) for t in grp]
+        _hip.require_f32(*M, *c, *wih, *wm, *[g for g, _ in tw + tm], *[g for g, _ in tb if g is not None])
+        ia, pa = _hip.int_array, _hip.ptr_array
+        n, D = ia([m.shape[0] for m in M]), ia([m.shape[1] for m in M])
+        dwm = pa([g for g, _ in tm])
+        nws = _hip.query("mmdfn_fold_back_workspace", len(grp), dwm, n, D, H)
+        if nws < 0:
+            raise _hip.HipLibraryError("mmdfn_fold_back_workspace rejected the terms (%d)" % nws)
+        ws = torch.empty(max(int(nws), 2), dtype=torch.float32, device=dev)
+        _hip.call("mmdfn_fold_back", len(grp), pa(M), pa(c), pa(wih), pa(wm), pa(bm), pa([g for g, _ in tw]), dwm,
+                  pa([g for g, _ in tb]), n, D, H, ia([a for _, a in tw]), ia([a for _, a in tm]), _hip.ptr(ws),
+                  _hip.ptr(_fold_tickets(dev)), _hip.stream())
+        for k in seen:
+            seen[k] = 1
 
 
 def _join_side():
@@ -386,6 +487,7 @@ def flush_queued_wgrads():
     if outs or ext:
         _flush_outs(outs, None, ext)
     _drain_riders()
+    _run_fold_back()         # behind every reduction launch: M and c are complete
 
 
 def _ext_destinations(ext):

@@ -57,9 +57,15 @@ def inventory(B, L, lengths, D_t, D_a, D_v, nl, P, n_act=2, He=200, d=100, C=6, 
         _cls("GRU l0 input contractions (party modalities + context, one grouped launch)", 1, **dense(n_act * R + R, He, G)),
         _cls("GRU l1 input contraction (context + party, one grouped launch)", 1, **dense(R + RP, He, G)),
         _cls("dX of GRU l1 (context + party, one grouped launch)", 1, **dense(R + RP, G, He)),
-        _cls("dX of party GRU l0", 1, **dense(n_act * R, G, He)),
-        _cls("dX of context GRU l0", 1, **dense(R, G, He)),
     ]
+    # input gradients of the l0 contractions: the context rider's is a K segment of the party launch; a modality whose raw
+    # width is at most He has none at all -- its weight gradients are folded back from dG^T u_m ('3-0-1': audio, text)
+    # ('3-0-1': the party modalities are audio and text, the context rider reads text; each modality folds on its own)
+    fold_a, fold_t = D_a <= He and D_a % 4 == 0, D_t <= He and D_t % 4 == 0
+    folded = fold_a or fold_t
+    dx_rows = (0 if fold_a else R) + (0 if fold_t else 2 * R)
+    if dx_rows:
+        fam["projections_hand_written"].append(_cls("dX of party + context GRU l0 (one grouped launch)", 1, **dense(dx_rows, G, He)))
     T = L
     step_us = GRU_MFMA_STEP_US if mfma_gru else GRU_CHAIN_US
     gru_f = 4.0 * seqs * T * (G + He + 2 * 4 * 100)            # gi in, y out, four saved gate tensors (both directions)
@@ -93,6 +99,10 @@ def inventory(B, L, lengths, D_t, D_a, D_v, nl, P, n_act=2, He=200, d=100, C=6, 
     wg = []
     for c in fam["projections_hand_written"][:3]:           # (the forward contractions: each has a weight gradient)
         wg.append((c["flops"], c["bytes"]))
+    # folded modalities: the l0 segments contract dG^T u_m (width D_m, not He) and linear_m has no segment of its own
+    for on, Dm, segs in ((fold_a, D_a, 1), (fold_t, D_t, 2)):
+        if on:
+            wg.append((2.0 * R * G * (Dm - He) * segs - 2.0 * R * Dm * He, 4.0 * R * (Dm - He) * segs))
     for c in fam["gcn_stack_fused"]:
         if "forward" in c["name"]:
             wg.append((c["flops"] * c["count"], 4.0 * MN * 6 * d * c["count"]))
@@ -103,6 +113,12 @@ def inventory(B, L, lengths, D_t, D_a, D_v, nl, P, n_act=2, He=200, d=100, C=6, 
              sum(b for _, b in wg), sum(f for f, _ in wg)),
         _cls("fixed-order reduction of the split partial sums", 1, 3 * 4.0e6),
     ]
+    if folded:
+        # dW_ih += M W_m^T + c b_m^T, dW_m += W_ih^T M for (party, a), (party, l), (context, l): operands and outputs once
+        Dsum_f = (D_a if fold_a else 0) + (2 * D_t if fold_t else 0)
+        fb_bytes = 4.0 * (G * Dsum_f + 4 * G * He + 4 * He * (D_a + D_t))
+        fb_flops = 4.0 * G * He * Dsum_f
+        fam["weight_gradients"].append(_cls("fold-back of the input projections (dW_ih, dW_m, db_m from dG^T u)", 1, fb_bytes, fb_flops))
     fam["encoder_glue"] = [
         _cls("party gather / scatter-combine, forward + backward (4 launches)", 4, 4.0 * (RP * He + R * He) * 1.0),
         _cls("dropout flags, the forward mask of the GRU inter-layer dropout (2 launches)", 2, 4.0 * R * He),
