@@ -636,7 +636,7 @@ int mmdfn_gemm_tn_batch_ext(int nseg, const float* const* A, const float* const*
                             void* riders, void* stream);
 
 /* Weight-gradient RIDERS of the GRU backward recurrence launch (ABI 17; the `riders` context: 18).  The backward recurrence of
- * nn.GRU (reference model.py:866-868: autograd of the context / party GRUs) keeps one CU per sequence busy for ~T x 0.75 us and leaves the other
+ * nn.GRU (reference model.py:866-868: autograd of the context / party GRUs) keeps one CU per sequence busy for ~T x 0.65 us and leaves the other
  * CUs idle (IEMOCAP batch of 16: 160 of 256).  mmdfn_wgrad_riders_stage takes the arguments of mmdfn_gemm_tn_batch, plans the
  * batch and allocates its slabs exactly as that call would, but -- when the batch runs on the bf16-piece form, has at most 16
  * segments and nothing is staged in `riders` yet -- stages it there instead of launching it: a mmdfn_gru_seq_bwd call given the
@@ -653,9 +653,9 @@ int mmdfn_wgrad_riders_stage(int nseg, const float* const* A, const float* const
                              const int* accumulate, float* workspace, void* riders, void* stream);
 int mmdfn_wgrad_riders_staged(void* riders);
 /* CUs the mmdfn_gru_seq_bwd launch of these groups leaves idle if it is of the kind that takes riders, else 0: stage a batch
- * only when this is > 0, and size it for that many CUs over the recurrence's ~0.75 us x T. */
+ * only when this is > 0, and size it for that many CUs over the recurrence's ~0.65 us x T. */
 int mmdfn_gru_seq_bwd_idle_cus(int ngroups, const int* rows);
-int mmdfn_gru_seq_bwd_step_ns(int ngroups, const int* rows);    /* ns per recurrence step of that launch (750 / 2300: the two forms) */
+int mmdfn_gru_seq_bwd_step_ns(int ngroups, const int* rows);    /* ns per recurrence step of that launch (650 / 2300: the two forms) */
 int mmdfn_wgrad_riders_flush(void* riders, void* stream);
 /* The slab reduction of a batch that rode (or that mmdfn_wgrad_riders_flush launched) is not a launch of its own either: it waits
  * in the context and joins the reduction launch of the next mmdfn_gemm_tn_batch / _ext call given that context (unless that call

@@ -20,9 +20,10 @@ TUNING_LIBPATH = os.path.join(LIBDIR, "libmmdfn_hip_tuning.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = "gfx950"
 # kernels whose vector-memory requests are asm statements with hand-counted waits: a register spill between a request and its wait
-# would store a register the load has not written yet.  (source file, substring of the mangled kernel name) -> the build fails
+# would store a register the load has not written yet.  source file -> substrings of the mangled kernel names: the build fails
 # unless hipcc reports ScratchSize 0 for every such kernel.
-NO_SPILL = {}        # (round 6's hand-counted form of linear_planes.hip measured equal to hipcc's schedule and was removed)
+# (gru.hip: the direct backward recurrence, gru_bwd_direct_body, in the plain launch <8, 4, 0, 1> and in the rider launch)
+NO_SPILL = {"gru.hip": ("gru_seq_bwd_kpart_kernelILi8ELi4ELi0ELi1E", "gru_seq_bwd_riders_kernelILb1E")}
 
 
 def sources():
@@ -107,17 +108,17 @@ def _build_locked(force, verbose, tuning):
 
 def _check_no_spill(remarks, watch, cmd):
     name = None
-    seen = 0
+    seen = set()
     for line in remarks.splitlines():
         if "Function Name:" in line:
             name = line.split("Function Name:")[1].split()[0]
-        elif "ScratchSize [bytes/lane]:" in line and name and watch in name:
-            seen += 1
+        elif "ScratchSize [bytes/lane]:" in line and name and any(w in name for w in watch):
+            seen.update(w for w in watch if w in name)
             if int(line.split("ScratchSize [bytes/lane]:")[1].split()[0]) != 0:
                 raise RuntimeError("%s spills registers (%s): its hand-counted vector-memory waits are only valid without "
                                    "scratch traffic" % (name, line.strip()))
-    if not seen:
-        raise RuntimeError("no resource-usage remark for kernels matching %r (%s)" % (watch, " ".join(cmd)))
+    if len(seen) != len(watch):
+        raise RuntimeError("no resource-usage remark for kernels matching %r (%s)" % (sorted(set(watch) - seen), " ".join(cmd)))
 
 
 def is_stale(tuning=False):

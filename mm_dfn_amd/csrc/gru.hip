@@ -18,6 +18,8 @@
 // Gate order r, z, n;  n = tanh(gi_n + r * (W_hn h + b_hn));  h = (1-z) n + z h_prev.
 #include "mmdfn_internal.h"
 #include "gemm_tn_split_body.h"
+#include <type_traits>
+#include <utility>
 #include "keep_flags_body.h"
 #include "../../include/mmdfn_hip.h"
 #include <stdlib.h>
@@ -1223,8 +1225,15 @@ __global__ __launch_bounds__(NT) void gru_seq_bwd_kernel(BwdGroups G) {
 // gradient dgh[38w + l] its wave needs next (the carry dh z is replicated in the up to three lanes that share a unit:
 // same inputs, same order, bit-identical).  LDS traffic per step: 0.5 KB of partials per wave; weight slices 76 VGPRs;
 // eight waves = two per SIMD (one wave per SIMD runs at ~10 cycles per instruction on this chain whatever the mix).
-// Same time-blocked global staging as above.  Used when every sequence gets its own workgroup in one round
-// (pick_r() == 1); larger batches keep the R = 2 / 4 kernels.  Variants and measurements: profiles/r02_gru_kernels.md.
+// Used when every sequence gets its own workgroup in one round (pick_r() == 1); larger batches keep the R = 2 / 4 kernels.
+// Variants and measurements: profiles/r02_gru_kernels.md.
+// Global traffic, two bodies:
+//  * gru_bwd_direct_body -- the plain (SEG = 0) launches, alone and with riders: every lane requests its own six operands
+//    BWD_RING_D steps ahead into registers and stores its own two results; no staged blocks (profiles/r14_gru_bwd_direct.md:
+//    86.1 -> 75.7 us per rider launch at cfg2, 71.7 us without riders).
+//  * gru_bwd_kpart_body -- the segmented (SEG = 1) launches: the time-blocked staging of the lane-pair kernel above (blocks of
+//    8 steps through LDS).  For SEG = 0 it is built into the tuning library only (MMDFN_GRU_BWD_STAGED=1): the A/B partner and
+//    bit-for-bit reference of the direct body.
 // =====================================================================================================
 constexpr int PU = 128;              // partial-sum row length, backward (100 units, padded)
 
@@ -1564,24 +1573,247 @@ __device__ __forceinline__ void gru_bwd_kpart_body(const BwdGroups& G, const int
     }
 }
 
-template <int NW, int GRP, int SEG>
+// The DIRECT form of the plain (SEG = 0) recurrence on eight waves: no staged blocks.  With 38 gate rows per wave a lane owns
+// ONE gate row jr = 38 wv + lane, so per step it needs six floats of its own unit (dy, r, z, n, ghn, h_prev) and produces two
+// (dgi[jr], dgh[jr]): every lane fetches its operands of step s + BWD_RING_D straight from global memory into a register ring
+// at the top of step s and stores its two results at the end of the step.  The row bases are wave-uniform (scalar registers,
+// one byte offset per lane); the loads are unconditional from clamped addresses (steps past the end repeat the last step's
+// row, h_prev's row is clamped into y, lanes without a gate row read unit 0) and what must not count is SELECTED away, so no
+// load leaves the arrays and none sits under a divergent condition.  What is left per step is the partial-sum exchange with
+// its one barrier: no in_s / out_s (8 KB of LDS instead of 66), no block loop, no block barriers, no index decode.
+// Same arithmetic in the same order as gru_bwd_kpart_body<8, 4, 0>: dgi and dgh are bit-identical.
+// Waits: vector-memory operations retire in order and vmcnt counts stores too, so step s may consume its operands with the
+// 6 loads of each of the D = BWD_RING_D steps requested since and the 2 stores of each of the D steps before it still in
+// flight: s_waitcnt vmcnt(8 D) behind the barrier, none in front of the matvec.  The ring has D + 1 slots in static registers:
+// the loop runs whole trips of D + 1 steps, the last T mod (D + 1) steps follow unrolled and request nothing (their operands
+// are in flight already).  Position k of a trip waits with min(8 D, 6 D + 2 k) -- in the first trip only k stores precede step
+// k -- and tail step j with 6 (D - 1 - j) + 2 j (valid with and without a trip in front of it).
+// The requests, the waits and the stores are asm statements counted by hand: left to hipcc the address temporaries landed in
+// ring registers with a load in flight (vmcnt(0) at the top of the step) and the row bases in VGPR pairs.  A slot is one
+// read-modify-write register chain through the loop (no copy of a register with a load in flight), and a spill between a
+// request and its wait would store a register the load has not written yet: build.py refuses scratch in these kernels (NO_SPILL).
+constexpr int BWD_RING_D = 4;
+constexpr int BWD_DIRECT_PART_B = 2 * 8 * PU * (int)sizeof(float);      // the partial sums: all the LDS the body touches
+// what the plain launch requests: more than half a CU's 160 KB, so that a CU holds ONE recurrence (a co-resident workgroup
+// slows the chain, profiles/r03_wgrad_overlap.md) -- mmdfn_gru_form's idle_cus counts on it
+constexpr int BWD_DIRECT_LDS = 84 * 1024;
+
+static_assert(GH == 100, "the plane offsets of the direct body's requests are literals: 400 / 800 / 1200 bytes");
+// one request: scalar row base + the lane's byte offset (+ a literal plane offset); the value is there behind vm_wait6
+#define GRU_VM_LOAD(dst, off, base, lit) \
+    asm volatile("global_load_dword %0, %1, %2" lit : "+v"(dst) : "v"(off), "s"(base))
+template <int N>
+__device__ __forceinline__ void vm_wait6(float (&r)[6]) {
+    asm volatile("s_waitcnt vmcnt(%6)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]) : "n"(N));
+}
+
+// the step's two results: dgi, and dgh nontemporal (read by the weight-gradient batch only)
+__device__ __forceinline__ void vm_store2(uint32_t off, float gi_v, float* pi, float gh_v, float* ph) {
+    asm volatile("global_store_dword %0, %1, %2" : : "v"(off), "v"(gi_v), "s"(pi) : "memory");
+    asm volatile("global_store_dword %0, %1, %2 nt" : : "v"(off), "v"(gh_v), "s"(ph) : "memory");
+}
+// f(integral_constant K) for K = 0 .. N-1; f for J, J+1, .. while J < min(rem, N) (nested: nothing is merged behind a step)
+template <class F, int... K>
+__device__ __forceinline__ void static_for(F& f, std::integer_sequence<int, K...>) {
+    (f(std::integral_constant<int, K>{}), ...);
+}
+template <int J, int N, class F>
+__device__ __forceinline__ void static_while(F& f, const int rem) {
+    if constexpr (J < N) {
+        if (J < rem) {
+            f(std::integral_constant<int, J>{});
+            static_while<J + 1, N>(f, rem);
+        }
+    }
+}
+
+__device__ __forceinline__ void gru_bwd_direct_body(const BwdGroups& G, const int bx, const int by, unsigned char* dyn) {
+    constexpr int NW = 8, GRP = 4;
+    constexpr int JPW = (3 * GH + NW - 1) / NW;     // 38 gate rows per wave: one per lane
+    constexpr int D = BWD_RING_D, NS = D + 1;
+    static_assert(JPW <= 64, "a lane owns one gate row");
+    static_assert(D >= 1 && D <= 7, "s_waitcnt vmcnt(8 D) must fit the 6-bit immediate");
+    float (*part)[NW][PU] = reinterpret_cast<float (*)[NW][PU]>(dyn);
+
+    int gidx = 0;
+    while (gidx + 1 < G.n && bx >= G.slice0[gidx + 1]) ++gidx;
+    const int dir = by;
+    const int row = bx - G.slice0[gidx];
+    const int T = G.T[gidx];
+    const int rows = G.rows[gidx];
+    if (T <= 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int j0 = JPW * wv;
+    const float* __restrict__ dy = G.dy[gidx];
+    const float* __restrict__ y = G.y[gidx];
+    const float* __restrict__ gates = G.gates[gidx];
+    const float* __restrict__ w_hh = G.w_hh[2 * gidx + dir];
+    float* __restrict__ dgi = G.dgi[gidx];
+    float* __restrict__ dgh = G.dgh[gidx];
+    static_assert(3 * GH - (NW - 1) * JPW > 0, "every wave owns a gate row");
+
+    // W_hh[j0 + jj][u] for the lane's two units u = lane, lane + 64 (< 100 for lane < 36); rows past 3H-1 carry zeros
+    const bool has1 = lane + 64 < GH;
+    f32x2 w[JPW];
+#pragma unroll
+    for (int jj = 0; jj < JPW; ++jj) {
+        const bool jok = j0 + jj < 3 * GH;
+        const int jc = jok ? j0 + jj : 3 * GH - 1;
+        w[jj][0] = jok ? w_hh[(int64_t)jc * GH + lane] : 0.f;
+        w[jj][1] = (jok && has1) ? w_hh[(int64_t)jc * GH + lane + 64] : 0.f;
+    }
+#pragma unroll
+    for (int jj = 0; jj < JPW; ++jj) pin_loaded(w[jj]);
+    // gate stage: lane l handles gate row j0 + l; a lane without one computes on unit 0 and stores nothing
+    const bool has = lane < JPW && j0 + lane < 3 * GH;
+    const int jr = has ? j0 + lane : 0;
+    const int gg = jr / GH;
+    const int uu = jr - gg * GH;
+    uint32_t uoff = (uint32_t)uu * 4u, joff = (uint32_t)jr * 4u;      // the lane's byte offsets: operands, results
+    float dv = 0.f, carry = 0.f;          // dgh[jr] of the previously processed step; dh z of unit uu
+
+    // Row bases, advanced by a constant stride per step (scalar registers): backward step f works on t = t0 + f dt.  The request
+    // bases stop at the last step (f = T-1: later requests repeat its row, their values are never consumed); h_prev of step f is
+    // y of t + dt = the row of step f + 1, clamped the same way (the last step's h_prev is selected to zero).
+    const int64_t dt = dir ? 1 : -1;
+    const int64_t o0 = (int64_t)(dir ? 0 : T - 1) * rows + row;
+    const int64_t st_y = dt * rows * (2 * GH), st_g = dt * rows * (8 * GH), st_o = dt * rows * (6 * GH);
+    const float* pd = dy + o0 * (2 * GH) + dir * GH;
+    const float* pg = gates + (o0 * 2 + dir) * (4 * GH);
+    const float* py = y + o0 * (2 * GH) + dir * GH + (T > 1 ? st_y : 0);
+    float* pi = dgi + o0 * (6 * GH) + dir * 3 * GH;
+    float* ph = dgh + o0 * (6 * GH) + dir * 3 * GH;
+    int f = 0;
+    // the six operands of the next backward step not requested yet
+    auto fetch = [&](float (&o6)[6]) {
+        GRU_VM_LOAD(o6[0], uoff, pd, "");
+        GRU_VM_LOAD(o6[1], uoff, pg, "");
+        GRU_VM_LOAD(o6[2], uoff, pg, " offset:400");
+        GRU_VM_LOAD(o6[3], uoff, pg, " offset:800");
+        GRU_VM_LOAD(o6[4], uoff, pg, " offset:1200");
+        GRU_VM_LOAD(o6[5], uoff, py, "");
+        pd += (f + 1 < T) ? st_y : 0;
+        pg += (f + 1 < T) ? st_g : 0;
+        py += (f + 2 < T) ? st_y : 0;
+        ++f;
+    };
+
+    float ring[NS][6];
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int e = 0; e < 6; ++e) ring[k][e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(ring[k]);
+
+    // one step: operands in iv behind s_waitcnt vmcnt(NC)
+    auto run_step = [&](auto NC, const int step, float (&iv)[6]) {
+        const int pb = step & 1;
+        // dh_prev partials of units (lane, lane + 64) over this wave's gate rows; dgh[j0 + jj] sits in lane jj of THIS wave
+        // (operands fetched four at a time: back-to-back v_readlane into distinct SGPRs, then the four FMAs -- a
+        // readlane directly followed by its consumer costs two wait states and serialises on one SGPR)
+        f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
+#pragma unroll
+        for (int j4 = 0; j4 < JPW; j4 += GRP) {
+            float dj[GRP];
+#pragma unroll
+            for (int e = 0; e < GRP; ++e) dj[e] = (j4 + e < JPW) ? lane_bcast(dv, j4 + e) : 0.f;
+            asm volatile("" : "+s"(dj[0]), "+s"(dj[1]), "+s"(dj[2]), "+s"(dj[3]));
+#pragma unroll
+            for (int e = 0; e < GRP; ++e) {
+                if (j4 + e >= JPW) continue;
+                const f32x2 dd = {dj[e], dj[e]};
+                if ((j4 + e) & 1) acc1 = __builtin_elementwise_fma(w[j4 + e], dd, acc1);
+                else acc0 = __builtin_elementwise_fma(w[j4 + e], dd, acc0);
+            }
+        }
+        part[pb][wv][lane] = acc0[0] + acc1[0];
+        part[pb][wv][lane + 64] = acc0[1] + acc1[1];       // (units >= 100 are padding)
+        __syncthreads();
+        float pr[NW];
+#pragma unroll
+        for (int w2 = 0; w2 < NW; ++w2) pr[w2] = part[pb][w2][uu];
+#pragma unroll
+        for (int sp = 1; sp < NW; sp *= 2)                         // fixed tree: bit-reproducible
+#pragma unroll
+            for (int w2 = 0; w2 + sp < NW; w2 += 2 * sp) pr[w2] += pr[w2 + sp];
+        const float rec = pr[0];
+        // the pre-activation gradient of gate row (g, u) from dh of unit u (every lane that shares the unit rebuilds the
+        // same dh and carries the same dh z)
+        vm_wait6<decltype(NC)::value>(iv);
+        const float dh = iv[0] + carry + rec;
+        const float rr = iv[1], zz = iv[2], nn = iv[3], ghn = iv[4];
+        const float hprev = (step < T - 1) ? iv[5] : 0.f;           // (the first forward step started from zero)
+        const float dn = dh * (1.0f - zz);
+        const float dz = dh * (hprev - nn);
+        carry = dh * zz;
+        // (n n rounded on its own, as hipcc builds the staged SEG = 0 body: it packs 1 - z and 1 - n n into one v_pk_add there
+        // and would contract this one into an fma here -- the two forms are bit-identical only with the same roundings; the
+        // empty asm keeps the product out of the contraction)
+        float nn2 = nn * nn;
+        asm("" : "+v"(nn2));
+        const float dnpre = dn * (1.0f - nn2);
+        const float drpre = dnpre * ghn * rr * (1.0f - rr);
+        const float dzpre = dz * zz * (1.0f - zz);
+        const float dghn = dnpre * rr;
+        const float gi_v = gg == 0 ? drpre : (gg == 1 ? dzpre : dnpre);
+        const float gh_v = gg == 0 ? drpre : (gg == 1 ? dzpre : dghn);
+        dv = gh_v;
+        // (everything that reads the slot is computed HERE, in front of the stores: the slot is requested again at the top of
+        // the next step, and a use sunk behind that request would make hipcc copy a register with a load in flight)
+        asm volatile("" : "+v"(carry), "+v"(dv));
+        if (has) {                    // (the math runs on every lane; only the two stores are masked.  Every wave has lanes
+                                      // with a gate row, so the two stores are always issued: the wait counts rely on it)
+            vm_store2(joff, gi_v, pi, gh_v, ph);
+        }
+        pi += st_o;
+        ph += st_o;
+    };
+
+    const int T_trips = T - T % NS;
+    for (int s0 = 0; s0 < T_trips; s0 += NS) {
+        auto trip_step = [&](auto K) {
+            constexpr int k = decltype(K)::value;
+            fetch(ring[(k + D) % NS]);
+            run_step(std::integral_constant<int, (6 * D + 2 * k < 8 * D ? 6 * D + 2 * k : 8 * D)>{}, s0 + k, ring[k]);
+        };
+        static_for(trip_step, std::make_integer_sequence<int, NS>{});
+    }
+    // the last T mod (D + 1) steps: operands requested by the prologue or the loop
+    auto tail_step = [&](auto J) {
+        constexpr int j = decltype(J)::value;
+        run_step(std::integral_constant<int, 6 * (D - 1 - j) + 2 * j>{}, T_trips + j, ring[j]);
+    };
+    static_while<0, D>(tail_step, T - T_trips);
+}
+
+// DIRECT = 1 (NW = 8, SEG = 0 only): the direct body above, its LDS the launch's dynamic request (BWD_DIRECT_LDS)
+template <int NW, int GRP, int SEG, int DIRECT = 0>
 __global__ __launch_bounds__(64 * NW) void gru_seq_bwd_kpart_kernel(BwdGroups G) {
-    gru_bwd_kpart_body<NW, GRP, SEG, false>(G, (int)blockIdx.x, (int)blockIdx.y, nullptr);
+    if constexpr (DIRECT) {
+        static_assert(NW == 8 && GRP == 4 && SEG == 0, "the direct body is the plain eight-wave recurrence");
+        extern __shared__ __attribute__((aligned(16))) unsigned char direct_smem[];
+        gru_bwd_direct_body(G, (int)blockIdx.x, (int)blockIdx.y, direct_smem);
+    } else {
+        gru_bwd_kpart_body<NW, GRP, SEG, false>(G, (int)blockIdx.x, (int)blockIdx.y, nullptr);
+    }
 }
 
 // The recurrence launch WITH RIDERS: workgroups [0, ngru) run the recurrence (bid -> (slot, direction) as the plain launch's
 // grid would), workgroups [ngru8, ...) run weight-gradient tiles of the step's queue (gemm_tn_split_body.h) that do not depend on
-// this recurrence.  The recurrence needs a CU per sequence for ~T x 0.75 us and leaves the other CUs idle (cfg2: 160 of 256 busy);
+// this recurrence.  The recurrence needs a CU per sequence for ~T x 0.65 us and leaves the other CUs idle (cfg2: 160 of 256 busy);
 // the launch's 108 KB of LDS per workgroup keeps every CU to ONE workgroup, so a rider never shares a CU with a recurrence
 // (whose latency chain a co-resident matrix kernel slows down, profiles/r03_wgrad_overlap.md), and the recurrences, having the
 // lowest block indices, are placed first.
 
+template <bool DIRECT>
 __global__ __launch_bounds__(512) void gru_seq_bwd_riders_kernel(const BwdGroups G, const TnRiderSegs rq, const int nslots,
                                                                  const int ngru8) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rider_smem[];
     const int bid = (int)blockIdx.x;
     if (bid < 2 * nslots) {
-        gru_bwd_kpart_body<8, 4, 0, true>(G, bid % nslots, bid / nslots, rider_smem);
+        if constexpr (DIRECT) gru_bwd_direct_body(G, bid % nslots, bid / nslots, rider_smem);
+        else gru_bwd_kpart_body<8, 4, 0, true>(G, bid % nslots, bid / nslots, rider_smem);
     } else if (bid >= ngru8) {
         tnsb::tns_block<0>(rq, bid - ngru8, rider_smem, nullptr);
     }
@@ -1696,6 +1928,19 @@ bool use_kpart_bwd() {
     return true;
 }
 
+// the eight-wave plain recurrence runs the direct body (gru_bwd_direct_body); the tuning build keeps the staged body
+// selectable (MMDFN_GRU_BWD_STAGED=1) as its A/B partner and bit-for-bit test reference
+bool use_staged_bwd() {
+#ifdef MMDFN_TUNING
+    const char* e = getenv("MMDFN_GRU_BWD_STAGED");
+    if (e != nullptr) return e[0] == '1';
+#endif
+    return false;
+}
+
+static_assert(BWD_DIRECT_PART_B <= BWD_DIRECT_LDS && BWD_DIRECT_PART_B <= tnsb::LDS_B, "the partial sums sit in the launch's LDS");
+static_assert(2 * BWD_DIRECT_LDS > 160 * 1024, "one recurrence workgroup per CU");
+
 int pick_r(int ngroups, const int* rows) {
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_R")) {        // A/B aid: force the rows per workgroup
@@ -1807,12 +2052,29 @@ extern "C" int mmdfn_gru_seq_bwd(int ngroups, const float* const* dy, const floa
             TnRiderSegs rq;
             mmdfn_seg_copy(rq, rp);
             const int ngru8 = (2 * sl + 7) & ~7;
-            if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel)) return e;
-            hipLaunchKernelGGL(gru_seq_bwd_riders_kernel, dim3(ngru8 + rp.wg_prefix[rp.n]), dim3(512), tnsb::LDS_B, s, G, rq, sl, ngru8);
+            const dim3 rgrid(ngru8 + rp.wg_prefix[rp.n]);
+#ifdef MMDFN_TUNING
+            if (use_staged_bwd()) {
+                if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel<false>)) return e;
+                hipLaunchKernelGGL(gru_seq_bwd_riders_kernel<false>, rgrid, dim3(512), tnsb::LDS_B, s, G, rq, sl, ngru8);
+                MMDFN_CHECK_LAUNCH();
+                return mmdfn_riders_launched(rd, s);
+            }
+#endif
+            if (int e = mmdfn_allow_big_lds(gru_seq_bwd_riders_kernel<true>)) return e;
+            hipLaunchKernelGGL(gru_seq_bwd_riders_kernel<true>, rgrid, dim3(512), tnsb::LDS_B, s, G, rq, sl, ngru8);
             MMDFN_CHECK_LAUNCH();
             return mmdfn_riders_launched(rd, s);
         }
-        hipLaunchKernelGGL((gru_seq_bwd_kpart_kernel<8, 4, 0>), grid, dim3(512), 0, s, G);
+#ifdef MMDFN_TUNING
+        if (use_staged_bwd()) {
+            hipLaunchKernelGGL((gru_seq_bwd_kpart_kernel<8, 4, 0>), grid, dim3(512), 0, s, G);
+            MMDFN_CHECK_LAUNCH();
+            return 0;
+        }
+#endif
+        if (int e = mmdfn_allow_big_lds(gru_seq_bwd_kpart_kernel<8, 4, 0, 1>)) return e;
+        hipLaunchKernelGGL((gru_seq_bwd_kpart_kernel<8, 4, 0, 1>), grid, dim3(512), BWD_DIRECT_LDS, s, G);
     }
     else if (R == 1) hipLaunchKernelGGL((gru_seq_bwd_kernel<1, 0>), grid, block, 0, s, G);
     else if (R == 2) hipLaunchKernelGGL((gru_seq_bwd_kernel<2, 0>), grid, block, 0, s, G);
@@ -1834,9 +2096,11 @@ extern "C" int mmdfn_gru_seq_fwd_takes_flags(int ngroups, const int* rows) {
     return mmdfn_gru_form(ngroups, rows).idle_cus > 0 ? 1 : 0;
 }
 
-// nanoseconds per recurrence step of that launch (what the rider batch's size is priced with)
+// nanoseconds per recurrence step of that launch (what the rider batch's size is priced with).  The eight-wave launch: the
+// direct body's launch time / T at cfg2 shapes without riders, 71.7 us / 110 (profiles/r14_gru_bwd_direct.md; the staged body
+// took 750)
 extern "C" int mmdfn_gru_seq_bwd_step_ns(int ngroups, const int* rows) {
-    return mmdfn_gru_form(ngroups, rows).mfma ? 2300 : 750;
+    return mmdfn_gru_form(ngroups, rows).mfma ? 2300 : 650;
 }
 
 extern "C" int mmdfn_gru_seq_fwd_seg(int ngroups, const float* const* gi, const float* const* w_hh,

@@ -369,7 +369,7 @@ def stage_riders(rows, T):
     idle = _hip.query("mmdfn_gru_seq_bwd_idle_cus", len(rows), _hip.int_array(rows))
     if idle <= 0:
         return riders
-    step_s = 1e-9 * _hip.query("mmdfn_gru_seq_bwd_step_ns", len(rows), _hip.int_array(rows))     # (0.75 us; the MFMA form 2.3)
+    step_s = 1e-9 * _hip.query("mmdfn_gru_seq_bwd_step_ns", len(rows), _hip.int_array(rows))     # (0.65 us; the MFMA form 2.3)
     budget = RIDER_BUDGET * idle * max(T) * step_s * _RIDER_FLOPS_PER_CU_S
     take, nseg, work = [], 0, 0.0
     for key, o in list(_WGQ["outs"].items()):
