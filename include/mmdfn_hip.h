@@ -878,6 +878,33 @@ int mmdfn_fold_back(int nterm, const float* const* M, const float* const* c, con
                     float* const* dbm, const int* n, const int* D, int H, const int* acc_wih, const int* acc_wm,
                     float* workspace, int32_t* tickets, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K13  Pass metrics accumulated on the device (ABI 23, additive; csrc/pass_stats.hip)
+ * ---------------------------------------------------------------------------
+ * One launch per step: ONE workgroup of mmdfn_pass_stats_threads() threads, fixed row -> thread assignment, counts through an
+ * LDS histogram of C x C integer counters (C <= mmdfn_pass_stats_max_classes()), added to the caller's accumulator with plain
+ * loads and stores -- launches that share an accumulator must be serialised on one stream.  Bit-reproducible; no scratch, no
+ * workspace.  logp: (N, C) contiguous fp32; target: N int64; loss: 1 fp32 or NULL; all in device memory, as is the accumulator:
+ *   pred      N int64          pred[i] = lowest index among the maxima of row i (torch.argmax); a row that holds a NaN predicts
+ *                              the index of its first NaN.  Written for EVERY row on EVERY launch, armed or not.
+ *   counts    C * C int64      counts[label * C + pred]
+ *   meta      8 int64          [0] armed  [1] rows  [2] batches  [3] bad_labels  [4] nan_rows  [5..7] reserved (never touched)
+ *   loss_sum  1 double
+ *   loss_hist slots fp32       the first `slots` batch losses of the pass, in launch order
+ * meta[armed] == 0: the launch writes pred and NOTHING else (warm-up and pre-capture launches of a captured step).
+ * Otherwise, for every row with target != ignore_index: 0 <= target < C -> counts[target * C + pred] += 1, meta[rows] += 1; any
+ * other label -> meta[bad_labels] += 1 and no cell; a NaN row among them -> meta[nan_rows] += 1 (ignored rows are counted
+ * nowhere).  Then once per launch: k = meta[batches]; loss_sum[0] += (double)loss[0]; if k < slots: loss_hist[k] = loss[0];
+ * meta[batches] = k + 1  (loss NULL: the batch is counted, the two loss updates are skipped).  The kernel never writes
+ * meta[armed]: the host does, with an ordinary fill, between launches.
+ * Returns -1 before any launch for N <= 0, C <= 0, C > max_classes, slots < 0, a null logp / target / pred / counts / meta /
+ * loss_sum, or a null loss_hist with slots > 0. */
+int mmdfn_pass_stats_threads(void);
+int mmdfn_pass_stats_max_classes(void);
+int mmdfn_pass_stats_accumulate(const float* logp, const int64_t* target, const float* loss, int64_t* pred, int64_t* counts,
+                                int64_t* meta, double* loss_sum, float* loss_hist, int64_t N, int C, int64_t ignore_index,
+                                int slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import random
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ops_stats
 
 
 def seed_everything(seed=2021):
@@ -64,6 +64,150 @@ def backward(loss):
             _loss_mod.UNIT_SEED_ACTIVE[0] = prev
 
 
+_OWN_BATCHES = 5      # word of PassStats' meta block that the launch never touches
+
+
+class PassStats:
+    """What a pass reports, accumulated where the step runs: a C x C confusion matrix (row = label), the counts of rows,
+    batches, bad labels and NaN rows, the float64 sum of the batch losses and the first ``loss_slots`` batch losses.  ``update``
+    is ONE launch per step on the device (ops.pass_stats_update, csrc/pass_stats.hip) -- a node of a captured step when a
+    StepGraphCache is given this object -- and ``fetch`` the one device -> host copy of a pass.
+
+    All of it lives in one int64 block that is allocated here and never re-pointed (a captured graph bakes its address):
+    word 0 ``armed`` | words 1-4 rows, batches, bad_labels, nan_rows | 5 this process's batches + 1 once ``all_reduce`` has run
+    (host-written) | 6-7 reserved | C * C counts | 1 word loss sum (float64) | loss history (float32).  ``armed`` is written by
+    the host only (``set_enabled``, as FlatAdam.set_enabled): while it is 0 a launch -- the replay of a captured one included --
+    writes its predictions and nothing else.  Host tensors take a plain torch restatement of the launch with the same rules."""
+
+    def __init__(self, n_classes, device, loss_slots=4096, ignore_index=-100):
+        self.n_classes, self.loss_slots, self.ignore_index = int(n_classes), int(loss_slots), int(ignore_index)
+        self.device = torch.device(device)
+        C = self.n_classes
+        if C <= 0 or self.loss_slots < 0:
+            raise ValueError("PassStats: n_classes > 0 and loss_slots >= 0, got %d / %d" % (C, self.loss_slots))
+        if self.device.type == "cuda" and C > ops.pass_stats_max_classes():
+            raise ValueError("PassStats: the device launch holds at most %d classes, got %d" % (ops.pass_stats_max_classes(), C))
+        M = ops_stats.META_WORDS
+        self._block = torch.zeros(M + C * C + 1 + (self.loss_slots + 1) // 2, dtype=torch.int64, device=self.device)
+        self._meta = self._block[:M]
+        self._counts = self._block[M:M + C * C]
+        self._loss_sum = self._block[M + C * C:M + C * C + 1].view(torch.float64)
+        self._loss_hist = self._block[M + C * C + 1:].view(torch.float32)[:self.loss_slots] if self.loss_slots else None
+        self._enabled = None
+        self._host = None
+        self.set_enabled(True)
+
+    def reset(self):
+        """Zero everything but ``armed`` with one fill launch.  Outside any graph."""
+        self._block[1:].zero_()
+        self._host = None
+
+    def set_enabled(self, flag):
+        """Write ``armed`` (one tiny fill, outside any graph; nothing when the word already holds ``flag``)."""
+        flag = bool(flag)
+        if flag != self._enabled:
+            self._meta[ops_stats.ARMED].fill_(int(flag))
+            self._enabled = flag
+
+    @property
+    def enabled(self):
+        return self._enabled
+
+    def update(self, log_prob, flat_labels, loss=None):
+        """Count one batch; returns its predictions (N int64; torch.argmax's rule).  Draws no random numbers, keeps nothing for
+        autograd."""
+        if log_prob.shape[1] != self.n_classes:
+            raise ValueError("PassStats.update: built for %d classes, got log-probabilities of %d" % (self.n_classes, log_prob.shape[1]))
+        args = (self._counts, self._meta, self._loss_sum, self._loss_hist, self.ignore_index)
+        if self.device.type != "cuda":
+            return ops.pass_stats_update_host(log_prob, flat_labels, loss, *args)
+        if loss is not None:
+            loss = loss.detach()
+            if loss.dtype != torch.float32:
+                loss = loss.to(torch.float32)
+        return ops.pass_stats_update(log_prob, flat_labels, loss, *args)
+
+    def all_reduce(self, group=None):
+        """SUM of the counts, of rows / batches / bad_labels / nan_rows and of the loss sum over the process group (gloo on host
+        tensors, RCCL on device tensors; never a graph node).  int64 sums are exact: every rank then derives the same metrics;
+        the float64 loss sum agrees across ranks to its summation order.  ``armed`` and the loss history stay local."""
+        import torch.distributed as dist
+        M, C = ops_stats.META_WORDS, self.n_classes
+        own = self._meta[ops_stats.BATCHES] + 1
+        dist.all_reduce(self._block[1:M + C * C], op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(self._loss_sum, op=dist.ReduceOp.SUM, group=group)
+        self._meta[_OWN_BATCHES].copy_(own)           # (a reserved word, zero on every rank while the sum ran)
+        self._host = None
+
+    def fetch(self):
+        """ONE device -> host copy of the whole block (the only synchronising call); the accessors below read that copy."""
+        self._host = self._block.cpu().numpy().copy()
+        return self
+
+    def _fetched(self):
+        if self._host is None:
+            raise RuntimeError("PassStats: fetch() first (the accessors read the host copy of the block)")
+        return self._host
+
+    def _word(self, w):
+        return int(self._fetched()[w])
+
+    rows = property(lambda self: self._word(ops_stats.ROWS))
+    batches = property(lambda self: self._word(ops_stats.BATCHES))
+    bad_labels = property(lambda self: self._word(ops_stats.BAD_LABELS))
+    nan_rows = property(lambda self: self._word(ops_stats.NAN_ROWS))
+
+    def confusion(self):
+        """(C, C) int64, row = label, column = prediction."""
+        M, C = ops_stats.META_WORDS, self.n_classes
+        return self._fetched()[M:M + C * C].reshape(C, C).copy()
+
+    def loss_sum(self):
+        M, C = ops_stats.META_WORDS, self.n_classes
+        return float(self._fetched()[M + C * C:M + C * C + 1].view(np.float64)[0])
+
+    def loss_mean(self):
+        return self.loss_sum() / self.batches if self.batches else float('nan')
+
+    def batch_losses(self):
+        """The first min(batches, loss_slots) batch losses (float32) of THIS process's pass, in step order."""
+        M, C = ops_stats.META_WORDS, self.n_classes
+        own = self._word(_OWN_BATCHES)
+        n = own - 1 if own else self.batches
+        return self._fetched()[M + C * C + 1:].view(np.float32)[:min(n, self.loss_slots)].copy()
+
+    # closed forms of the matrix, in float64
+    def accuracy(self):
+        cm = self.confusion()
+        n = int(cm.sum())
+        return float(np.trace(cm)) / n if n else float('nan')
+
+    def weighted_f1(self):
+        """Per-class F1 = 2 tp / (2 tp + fp + fn) (0 for a class with neither predicted nor true samples) weighted by support:
+        sklearn's f1_score(average='weighted') under its default zero-division rule."""
+        cm = self.confusion().astype(np.float64)
+        n = cm.sum()
+        if n == 0:
+            return float('nan')
+        tp, support = np.diag(cm), cm.sum(1)
+        denom = support + cm.sum(0)                # 2 tp + fn + fp
+        f1 = np.divide(2.0 * tp, denom, out=np.zeros_like(tp), where=denom > 0)
+        return float((f1 * support).sum() / n)
+
+    def per_class_accuracy(self):
+        """Recall of every class; nan for a class without true samples."""
+        cm = self.confusion().astype(np.float64)
+        support = cm.sum(1)
+        return np.divide(np.diag(cm), support, out=np.full(self.n_classes, np.nan), where=support > 0)
+
+    def as_arrays(self):
+        """(labels, preds): the matrix expanded, grouped by (label, pred) -- NOT in utterance order.  Every order-invariant
+        metric of these arrays is that of the pass's real sequences."""
+        C = self.n_classes
+        cells = self.confusion().ravel()
+        return np.repeat(np.repeat(np.arange(C), C), cells), np.repeat(np.tile(np.arange(C), C), cells)
+
+
 class StepGraphCache:
     """Shape-keyed hipGraph cache for the pass loop: one captured step per batch signature (dialogue lengths, padded
     shape, train / eval), replayed whenever that signature comes back.
@@ -79,7 +223,8 @@ class StepGraphCache:
 
     IGNORE = -100                  # label of the padding dialogue's utterances (bucketed entries)
 
-    def __init__(self, model, loss_f, max_entries=96, warmup=2, bucket_rows=0, larger_bucket_fallback=True, optimizer=None):
+    def __init__(self, model, loss_f, max_entries=96, warmup=2, bucket_rows=0, larger_bucket_fallback=True, optimizer=None,
+                 pass_stats=None):
         """``bucket_rows`` = g > 0: BUCKETED entries -- one captured step per (train / eval, B, padded length L, ceil((N + 1) /
         g) g) instead of per exact tuple of dialogue lengths (N = the batch's utterances).  The batch is padded to its
         bucket with ONE extra dialogue of 1..g utterances (fixed random features, labels IGNORE: dialogues never interact
@@ -101,8 +246,19 @@ class StepGraphCache:
         ``optimizer``: a device-state FlatAdam (``capturable=True`` / ``max_grad_norm`` / ``skip_nonfinite``) captured into every
         TRAINING entry, exact and bucketed (graphs.CapturedStep(optimizer=...)); eval entries are captured without it.  The pass
         loop must then not step it again (train_or_eval_graph_model does not), and ``precapture`` replays with the update
-        disabled."""
+        disabled.
+        ``pass_stats``: a PassStats (built with ignore_index = IGNORE, the label of the bucketed entries' padding rows).  Every
+        entry, exact and bucketed, train and eval, then counts its batch with ``pass_stats.update(log_prob, labels, loss)`` as
+        a node of the captured step, in place of the ``torch.argmax`` launch (``last_pred`` is that launch's output).  Only
+        replays count: the block is disarmed on the device while a step is warmed up and captured and for the whole of
+        ``precapture``, and armed again in front of a replay -- a miss in the middle of a pass counts its batch exactly once,
+        through the replay that follows the capture."""
         from collections import OrderedDict
+        if pass_stats is not None and pass_stats.ignore_index != self.IGNORE:
+            raise ValueError("StepGraphCache: pass_stats must ignore the padding label (PassStats(ignore_index=%d)), got %d"
+                             % (self.IGNORE, pass_stats.ignore_index))
+        self.pass_stats = pass_stats
+        self._stats_hold = False           # precapture: replays leave the block disarmed as well
         if optimizer is not None and not getattr(optimizer, "device_state", False):
             raise ValueError("StepGraphCache: optimizer= needs a FlatAdam on device-resident step state (capturable=True, "
                              "max_grad_norm or skip_nonfinite)")
@@ -125,6 +281,18 @@ class StepGraphCache:
                 # (torch's default ignore_index IS -100: the usual object is taken as it is)
                 self._loss_ign = loss_f if loss_f.ignore_index == self.IGNORE else NLLLoss(
                     weight=loss_f.weight, ignore_index=self.IGNORE, reduction=loss_f.reduction)
+
+    def _capture(self, fn, train_flag):
+        """A CapturedStep of ``fn``; its eager warm-up passes and the capture itself run with the pass statistics disarmed."""
+        from .graphs import CapturedStep
+        if self.pass_stats is not None:
+            self.pass_stats.set_enabled(False)
+        return CapturedStep(self.model, fn, warmup=self.warmup, optimizer=self.optimizer if train_flag else None)
+
+    def _replay(self, cap):
+        if self.pass_stats is not None:
+            self.pass_stats.set_enabled(not self._stats_hold)      # (host bookkeeping; a fill only when the word changes)
+        return cap.replay()
 
     def _hand_over_grads(self, ent):
         """``p.grad`` = the gradient tensors the entry's graph writes (walking named_parameters() on every step cost the
@@ -171,12 +339,20 @@ class StepGraphCache:
         self._exact_buckets = True
         if self.optimizer is not None:
             self.optimizer.set_enabled(False)
+        stats_were = None
+        if self.pass_stats is not None:
+            stats_were = self.pass_stats.enabled
+            self._stats_hold = True
+            self.pass_stats.set_enabled(False)
         try:
             made = self._precapture_walk(loader, train_flag, device)
         finally:
             self._exact_buckets = False
             if self.optimizer is not None:
                 self.optimizer.set_enabled(True)
+            if self.pass_stats is not None:
+                self._stats_hold = False
+                self.pass_stats.set_enabled(stats_were)
         if hasattr(loader, "bind_graph_cache"):
             self.forget_queued()
         for p, g in grads:
@@ -204,7 +380,6 @@ class StepGraphCache:
 
     def _step_bucketed(self, inputs, lengths, train_flag):
         """One step through a bucketed entry (see __init__).  Returns (loss, log_prob[:N], flat_labels[:N])."""
-        from .graphs import CapturedStep
         from .layout import IndexScope
         g = self.bucket_rows
         lengths = [int(x) for x in lengths]
@@ -251,7 +426,7 @@ class StepGraphCache:
             tri = (torch.arange(L, device=dev).unsqueeze(0) < torch.arange(L + 1, device=dev).unsqueeze(1))
             tri_q, tri_u = tri.to(qmask.dtype), tri.to(umask.dtype)
             out = {}
-            model, loss_f = self.model, self._loss_ign
+            model, loss_f, stats = self.model, self._loss_ign, self.pass_stats
             with scope:
                 pos = scope.tensor(("labelpos", Lp), lens2, label_pos, dev)
             flat = label.reshape(-1).index_select(0, pos)
@@ -268,8 +443,11 @@ class StepGraphCache:
                 with scope:
                     torch.index_select(label.reshape(-1), 0, pos, out=flat)
                     out["log_prob"] = model(textf, qmask, umask, state["lens2"], acouf, visuf, False)[0]
-                    out["pred"] = torch.argmax(out["log_prob"], 1)
+                    if stats is None:
+                        out["pred"] = torch.argmax(out["log_prob"], 1)
                     loss = loss_f(out["log_prob"], flat)
+                    if stats is not None:                      # predictions + this batch's counts: one launch, no argmax
+                        out["pred"] = stats.update(out["log_prob"], flat, loss)
                     if train_flag:
                         backward(loss)
                 return loss
@@ -277,7 +455,7 @@ class StepGraphCache:
             mode = model.training
             model.train(train_flag)
             with torch.set_grad_enabled(bool(train_flag)):
-                cap = CapturedStep(model, fn, warmup=self.warmup, optimizer=self.optimizer if train_flag else None)
+                cap = self._capture(fn, train_flag)
             model.train(mode)
             ent = dict(static=static, cap=cap, out=out, flat=flat, pos=pos, pending=None, scope=scope, set_padding=set_padding,
                        state=state, bucketed=True, B=B)
@@ -301,7 +479,7 @@ class StepGraphCache:
                     torch._foreach_copy_([x[0] for x in grp], [x[1] for x in grp], non_blocking=True)
         cap = ent["cap"]
         try:
-            loss = cap.replay()
+            loss = self._replay(cap)
         except RuntimeError as exc:
             if "storage moved" not in str(exc):
                 raise
@@ -349,7 +527,6 @@ class StepGraphCache:
     def step(self, inputs, lengths, train_flag, test_label=False):
         """inputs = (textf, visuf, acouf, qmask, umask, label) on the device.  Returns (loss, log_prob, flat_labels):
         tensors owned by the cache entry -- consume (or clone) them before this signature is stepped again."""
-        from .graphs import CapturedStep
         key = self.signature([t.shape for t in inputs], lengths, train_flag, test_label)
         if self.bucket_rows and self._bucketable(inputs, lengths, test_label):
             return self._step_bucketed(inputs, lengths, train_flag)
@@ -375,13 +552,16 @@ class StepGraphCache:
             pos = torch.cat([torch.arange(int(n)) + j * Lp for j, n in enumerate(lengths)]).to(label.device)
             flat = label.reshape(-1).index_select(0, pos)
             out = {}
-            model, loss_f = self.model, self.loss_f
+            model, loss_f, stats = self.model, self.loss_f, self.pass_stats
 
             def fn():
                 torch.index_select(label.reshape(-1), 0, pos, out=flat)     # inside the graph: this batch's labels
                 out["log_prob"] = model(textf, qmask, umask, lengths, acouf, visuf, test_label)[0]
-                out["pred"] = torch.argmax(out["log_prob"], 1)          # (the pass loop's per-step metric input)
+                if stats is None:
+                    out["pred"] = torch.argmax(out["log_prob"], 1)          # (the pass loop's per-step metric input)
                 loss = loss_f(out["log_prob"], flat)
+                if stats is not None:                          # predictions + this batch's counts: one launch, no argmax
+                    out["pred"] = stats.update(out["log_prob"], flat, loss)
                 if train_flag:
                     backward(loss)
                 return loss
@@ -389,7 +569,7 @@ class StepGraphCache:
             mode = model.training
             model.train(train_flag)
             with torch.set_grad_enabled(bool(train_flag)):
-                cap = CapturedStep(model, fn, warmup=self.warmup, optimizer=self.optimizer if train_flag else None)
+                cap = self._capture(fn, train_flag)
             model.train(mode)
             # everything the graph reads that was allocated OUTSIDE the capture must live as long as the graph: the
             # static inputs, the label gather index and the flattened labels (the closure itself is kept by cap)
@@ -412,7 +592,7 @@ class StepGraphCache:
         ent["reserved"] = False
         cap = ent["cap"]
         try:
-            loss = cap.replay()
+            loss = self._replay(cap)
         except RuntimeError as exc:
             if "storage moved" not in str(exc):
                 raise
@@ -435,12 +615,29 @@ class StepGraphCache:
 
 def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=False, optimizer=None, cuda_flag=False,
                               modals=None, target_names=None, test_label=False, tensorboard=False, seed=2021,
-                              step_hook=None, graph_cache=None):
+                              step_hook=None, graph_cache=None, device_metrics=False, reduce_group=None):
     """``graph_cache``: a StepGraphCache (or None = launch every step eagerly, as before).  A cache that owns its optimizer
     (StepGraphCache(optimizer=...)) steps it inside the replayed graph: ``optimizer`` must be that object, there is no place
     for a ``step_hook`` between backward and update, and only steps that bypass the cache (``test_label``) call
-    ``optimizer.step()`` here."""
+    ``optimizer.step()`` here.
+    ``device_metrics=True``: the pass keeps no per-step predictions, labels or losses.  Every step adds its batch to a PassStats
+    -- ``graph_cache.pass_stats``, counted by a node of the replayed step, or a private one for the eager loop (classes from the
+    first ``log_prob``, device from the batch) -- which is read back ONCE at the end; accuracy, weighted F1 and the per-class
+    figures are closed forms of its confusion matrix, ``avg_loss`` the float64 mean of the batch losses.  Same 8-tuple, but
+    positions 4 and 5 hold the matrix expanded (PassStats.as_arrays: grouped by (label, prediction), NOT in utterance order --
+    metrics that need the order, ``vids`` alignment, keep the default path).  ``reduce_group``: a process group the statistics
+    are summed over before they are read (data parallelism: every rank then reports the same global metrics; the per-batch
+    losses of the last position stay this rank's).  A cache without a ``pass_stats`` raises ValueError."""
     losses, preds, labels = [], [], []
+    stats, nsteps = None, 0
+    if device_metrics:
+        if graph_cache is not None:
+            stats = getattr(graph_cache, "pass_stats", None)
+            if stats is None:
+                raise ValueError("train_or_eval_graph_model: device_metrics=True needs a StepGraphCache built with pass_stats= "
+                                 "(its captured steps would keep the per-step book-keeping otherwise)")
+            stats.set_enabled(True)
+            stats.reset()
     assert not train_flag or optimizer is not None
     in_graph_opt = graph_cache is not None and getattr(graph_cache, "optimizer", None) is not None
     if in_graph_opt and train_flag:
@@ -467,25 +664,34 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
             stepped_in_graph = in_graph_opt and train_flag
             loss, log_prob, flat = graph_cache.step((textf, visuf, acouf, qmask, umask, label), lengths, train_flag,
                                                     test_label)
-            # metrics are deferred to the end of the pass: the step's predictions, labels and loss stay where the graph
-            # wrote them (no per-step copy launches) unless this cache entry is stepped again before the pass ends, in
-            # which case they are copied out first (StepGraphCache runs the entry's ``pending`` closure)
-            ent = graph_cache.last_entry
-            slot = len(preds)
-            preds.append(graph_cache.last_pred)
-            labels.append(flat)
-            losses.append(loss.detach())
+            nsteps += 1
+            # (device_metrics: the replayed step counted this batch itself -- nothing of the entry is referenced after the step)
+            if stats is None:
+                # metrics are deferred to the end of the pass: the step's predictions, labels and loss stay where the graph
+                # wrote them (no per-step copy launches) unless this cache entry is stepped again before the pass ends, in
+                # which case they are copied out first (StepGraphCache runs the entry's ``pending`` closure)
+                ent = graph_cache.last_entry
+                slot = len(preds)
+                preds.append(graph_cache.last_pred)
+                labels.append(flat)
+                losses.append(loss.detach())
 
-            def materialise(slot=slot):
-                preds[slot], labels[slot], losses[slot] = preds[slot].clone(), labels[slot].clone(), losses[slot].clone()
-            ent["pending"] = materialise
+                def materialise(slot=slot):
+                    preds[slot], labels[slot], losses[slot] = preds[slot].clone(), labels[slot].clone(), losses[slot].clone()
+                ent["pending"] = materialise
         else:
             log_prob, e_i, e_n, e_t, e_l = model(textf, qmask, umask, lengths, acouf, visuf, test_label)
             flat = flatten_labels(label, lengths)
             loss = loss_f(log_prob, flat)
-            preds.append(torch.argmax(log_prob, 1))
-            labels.append(flat)
-            losses.append(loss.detach())
+            nsteps += 1
+            if device_metrics:
+                if stats is None:         # no cache: a private block, sized by the first batch
+                    stats = PassStats(log_prob.shape[1], log_prob.device)
+                stats.update(log_prob, flat, loss)
+            else:
+                preds.append(torch.argmax(log_prob, 1))
+                labels.append(flat)
+                losses.append(loss.detach())
             if train_flag:
                 backward(loss)
         if train_flag:
@@ -496,19 +702,29 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
                 optimizer.step()
         if len(data) > 6:
             vids = data[6]
-    if not preds:
+    if not nsteps:
         return [], [], float('nan'), float('nan'), [], [], float('nan'), []
     if graph_cache is not None:
         for ent in graph_cache.entries.values():
             ent["pending"] = None             # everything is consumed right below
-    preds = torch.cat(preds).cpu().numpy()
-    labels = torch.cat(labels).cpu().numpy()
-    losses = torch.stack(losses).cpu().numpy()
-    avg_loss = round(float(np.sum(losses)) / len(losses), 4)
     from sklearn import metrics
     from sklearn.metrics import accuracy_score, f1_score
-    avg_accuracy = round(accuracy_score(labels, preds) * 100, 2)
-    avg_fscore = round(f1_score(labels, preds, average='weighted') * 100, 2)
+    if device_metrics:
+        if reduce_group is not None:
+            stats.all_reduce(reduce_group)
+        stats.fetch()                         # the pass's one device -> host copy
+        labels, preds = stats.as_arrays()
+        losses = stats.batch_losses()
+        avg_loss = round(stats.loss_mean(), 4)
+        avg_accuracy = round(stats.accuracy() * 100, 2)
+        avg_fscore = round(stats.weighted_f1() * 100, 2)
+    else:
+        preds = torch.cat(preds).cpu().numpy()
+        labels = torch.cat(labels).cpu().numpy()
+        losses = torch.stack(losses).cpu().numpy()
+        avg_loss = round(float(np.sum(losses)) / len(losses), 4)
+        avg_accuracy = round(accuracy_score(labels, preds) * 100, 2)
+        avg_fscore = round(f1_score(labels, preds, average='weighted') * 100, 2)
     all_each, all_acc = "", ["ACC"]
     if target_names is not None:
         all_each = metrics.classification_report(labels, preds, target_names=target_names, digits=4,
@@ -521,23 +737,31 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
 
 
 def fit(model, loss_f, optimizer, train_loader, valid_loader, test_loader, n_epochs, patience=10, valid_rate=0.1,
-        cuda_flag=False, modals=None, target_names=None, run_pass=None, log=print, step_hook=None, graph_cache=None):
+        cuda_flag=False, modals=None, target_names=None, run_pass=None, log=print, step_hook=None, graph_cache=None,
+        device_metrics=False, reduce_group=None):
     """The epoch loop of run_train_erc.py:531-660: train / valid / test pass per epoch, model selection on the
     validation weighted-F1 (on the test split when valid_rate == 0), and the DUAL-patience early stop -- the run
     ends only when neither the F1 (strict improvement, :614-618) nor the loss (:619-627) has improved for
     ``patience`` epochs (:637).  Returns the history and the test metrics at the two selected epochs (:641-660).
 
     ``graph_cache=True`` replays a captured step per batch signature (StepGraphCache) instead of launching eagerly.
+    ``device_metrics`` / ``reduce_group``: handed to every pass (train_or_eval_graph_model); ``graph_cache=True`` then builds
+    the cache with a PassStats (classes from ``model.smax_fc``).  With ``reduce_group`` the stopping rule sees the same global
+    F1 and loss on every rank.
     ``run_pass(loader, epoch, train_flag) -> (all_each, all_acc, loss, acc, labels, preds, fscore, extras)``
     defaults to ``train_or_eval_graph_model``; tests drive the stopping rule with a stub."""
     if graph_cache is True:
-        graph_cache = StepGraphCache(model, loss_f)
+        stats = None
+        if device_metrics:
+            stats = PassStats(model.smax_fc.out_features, next(model.parameters()).device, ignore_index=StepGraphCache.IGNORE)
+        graph_cache = StepGraphCache(model, loss_f, pass_stats=stats)
     if run_pass is None:
         def run_pass(loader, epoch, train_flag):
             return train_or_eval_graph_model(model, loss_f, loader, epoch=epoch, train_flag=train_flag,
                                              optimizer=optimizer if train_flag else None, cuda_flag=cuda_flag,
                                              modals=modals, target_names=target_names, step_hook=step_hook,
-                                             graph_cache=graph_cache)
+                                             graph_cache=graph_cache, device_metrics=device_metrics,
+                                             reduce_group=reduce_group)
     hist = dict(train_loss=[], train_fscore=[], valid_loss=[], valid_fscore=[], test_loss=[], test_acc=[], test_fscore=[])
     best_epoch, best_epoch2, pat, pat2, best_eval_fscore, best_eval_loss = -1, -1, 0, 0, 0, None
     last = None
