@@ -1,7 +1,10 @@
 """autograd.Functions over the C-ABI kernels (libmmdfn_hip.so) -- the FACADE: the operators live in `ops_*.py`, one module per
 group (round 6 split of a 2 000-line file); every name, private ones included, is re-exported here, so `ops.X` keeps working.
-Module-level state that is REBOUND (not mutated) must be patched in its own module: `ops_wgrad._prepare_wgrad_batch`,
-`ops_flags.draw_flags`, `ops_flags._FLAG_SCOPE`.
+Module-level names that are REBOUND (not mutated) must be set or patched in their own module, the copy here does not follow:
+`ops_wgrad._prepare_wgrad_batch`, the switches `ops_wgrad.EARLY_WGRAD` / `SLAB_RIDE` (`RIDERS`, `RIDER_BUDGET` and `RIDER_LOG` are
+not re-exported for that reason), `ops_flags.draw_flags`, `ops_flags._FLAG_SCOPE`.  The graph-done hook and the side stream of
+`ops_wgrad` are rebound too and have no copy here: `set_graph_backward_done_hook` sets the former.  The running backward pass,
+`ops_wgrad._PASS`, is ONE object that is re-initialised in place and never rebound: `ops._PASS` is that object.
 
 Every function launches hand-written gfx950 kernels on the current HIP stream.  There is no CPU / eager fallback: CPU
 tensors raise.
@@ -18,12 +21,12 @@ from .ops_graph import (  # noqa: F401
     build_band_adjacency,
 )
 from .ops_wgrad import (  # noqa: F401
-    colsum, _strided_rows, gemm_tn_supported, gemm_tn, gemm_tn_grouped, _WGQ, EARLY_WGRAD, _WG_MAX, wgrad_batch,
+    colsum, _strided_rows, gemm_tn_supported, gemm_tn, gemm_tn_grouped, _PASS, EARLY_WGRAD, _WG_MAX, wgrad_batch,
     wgrad_batching, _leaf, _hooked, _queueable, queue_wgrad, SLAB_RIDE, slab_reduce_queueable, queue_slab_reduce,
-    _join_side, _GRAPH_DONE_HOOK, set_graph_backward_done_hook, flush_queued_wgrads_now, flush_queued_wgrads_early,
-    _GRAD_ADDENDS, _GRAD_ADDENDS_ARMED, drop_grad_addends, add_grad_addends, apply_grad_addends, flush_queued_wgrads,
+    queue_fold_back, fold_back_queueable, set_graph_backward_done_hook, flush_queued_wgrads_now, flush_queued_wgrads_early,
+    drop_grad_addends, add_grad_addends, apply_grad_addends, flush_queued_wgrads,
     _ext_destinations, _flush_outs, _launch_wgrad_batch, _prepare_wgrad_batch, join_weight_grads,
-    set_async_weight_grads, _wgrad_inline, _wgrad, stage_riders, finish_riders,
+    _wgrad_inline, _wgrad, stage_riders, finish_riders,
 )
 from .ops_linear import (  # noqa: F401
     linear_raw, linear_group_raw, linear_group_supported, dense_nk, dense_kn, linear_supported, linear_preferred,

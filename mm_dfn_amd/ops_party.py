@@ -8,8 +8,8 @@ import torch
 from . import _hip
 from . import ops_linear
 from .ops_linear import _wgrad, linear_group_raw
-from .ops_wgrad import (_WGQ, _queueable, _wgrad_inline, colsum, flush_queued_wgrads, fold_back_queueable, queue_fold_back,
-                        queue_wgrad, slab_reduce_queueable)
+from .ops_wgrad import (_queueable, _wgrad_inline, colsum, fold_back_queueable, queue_fold_back, queue_slab_reduce, queue_wgrad,
+                        slab_reduce_queueable)
 
 
 class _PartyGather(torch.autograd.Function):
@@ -99,10 +99,8 @@ def _queue_bias_halves(A, b1, b2, n1, slabs=None):
             raise _hip.HipLibraryError("mmdfn_colsum_partial rejected the operand (%d)" % nsl)
     buf = torch.empty(N, dtype=torch.float32, device=A.device)
     b1.grad, b2.grad = buf[:n1], buf[n1:]
-    _WGQ["ext"].append(dict(part=None, colpart=ws, splits=int(nsl), M=int(N), N=0, weight=None, bias=_HalvesGrad(buf), acc=0))
-    if not _WGQ["armed"]:
-        _WGQ["armed"] = True
-        torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
+    # acc=0, said here: the stand-in HAS a .grad, but buf is uninitialised memory -- the reduction writes it, it must not add to it
+    queue_slab_reduce(None, ws, nsl, N, 0, biases=[_HalvesGrad(buf)], acc=0)
 
 
 # _ProjectGather.forward: the plane projection stores its rows in party order and writes rank and the padding rows itself ("0": the

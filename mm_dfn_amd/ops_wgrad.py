@@ -100,64 +100,111 @@ def gemm_tn_grouped(problems):
 #     train.backward / ops.wgrad_batch() on a DDP-wrapped model (the queued parameters would bypass the reducer) -- use the
 #     package's own GradientBucket (distributed.py), or a plain loss.backward();
 #   * non-leaf weights always take the in-line path.
-# The queue belongs to one backward pass: entering the outermost scope drops anything a failed backward left behind, and
-# leaving it flushes what the engine callback did not (or clears the queue when the backward raised).
 # ---------------------------------------------------------------------------------------------------
-# "riders": the backward pass's rider context (_hip.riders_context(), from entering the outermost scope to leaving it) -- every
-# weight-gradient batch launched inside the scope is given it, so that the slab reductions of rider batches waiting there join
-# (or, sharing a destination, go before) the next reduction launch.
-_WGQ = {"segs": [], "outs": {}, "ext": [], "armed": False, "scope": 0, "side": None, "held": [], "pending_join": False,
-        "riders": None, "rider_keep": None, "rider_held": []}
 # MMDFN_EARLY_WGRAD=1: issue the graph-side weight gradients (GCN stack, LSTM gate) on a second stream as soon as the graph
 # part of the backward pass is done, concurrently with the GRU backward recurrence.  OFF by default: measured slower at
 # cfg2 (1.133 vs 1.107 ms per step; the split batches cost 47.6 + 111.5 us against 140.3 us for one, and the concurrent
 # recurrence slows from 82.8 to 89.0 us -- timeline in profiles/r03_wgrad_overlap.md).  Kept because it is where a
 # two-part gradient bucket would start its first all-reduce on a multi-GPU node.
 EARLY_WGRAD = __import__("os").environ.get("MMDFN_EARLY_WGRAD", "0") == "1"
-_WG_MAX = 40        # TN_MAXSEG / TN_MAXOUT of csrc/gemm_tn.hip
+_WG_MAX = 40        # MMDFN_TNS_MAXSEG of csrc/mmdfn_internal.h (segments, and outputs, of one batch launch)
 # Riders (MMDFN_WGRAD_RIDERS=0 turns them off): what is queued when a GRU backward recurrence is about to be launched -- the
 # graph side's weight gradients in front of the second GRU layer's recurrence, that layer's own in front of the first layer's --
 # does not wait for the end of the pass: its tiles run as extra workgroups of the recurrence launch, on the CUs the recurrence
 # leaves idle (csrc/gru.hip gru_seq_bwd_riders_kernel, include/mmdfn_hip.h mmdfn_wgrad_riders_stage).
 RIDERS = __import__("os").environ.get("MMDFN_WGRAD_RIDERS", "1") == "1"
 _RIDER_MAXSEG = 16  # MMDFN_RIDER_MAXSEG of csrc/mmdfn_internal.h
+# Process-lifetime state, NOT part of a backward pass (untouched when a pass begins or ends): RIDER_LOG, the side stream (created
+# once, reused), the graph-done hook (set BEFORE the pass it is meant for opens its scope), the fold-back tickets (_FOLD_TICKETS).
 RIDER_LOG = None    # a list: stage_riders appends what it found queued and what it took (tools/rider_log.py)
+_side_stream = _graph_done_hook = None      # flush_queued_wgrads_early's second stream; set_graph_backward_done_hook's function
 
 
-class wgrad_batch:
-    """``with ops.wgrad_batch(): loss.backward()`` -- weight gradients of leaf parameters are batched into one launch pair
-    and written to ``.grad`` directly (see the comment above).  Re-entrant; exception-safe."""
+class _BackwardPass:
+    """THE backward pass that is running, and the ``wgrad_batch()`` scope around it.  ONE instance per process (_PASS), re-initialised
+    in place and never rebound: the package runs one backward pass at a time (autograd runs custom backward functions on its engine
+    thread, so a thread-local would be wrong).  Entering the outermost scope starts from a fresh pass, leaving it finishes the pass;
+    ``reset()`` alone clears the fields.  Gradient addends are also registered by a plain ``loss.backward()`` outside any scope
+    (gru._GruTable): they leave with their end-of-backward callback -- or, when that backward raised, with the next pass that begins."""
+    depth = 0                       # nesting of the scopes: only the outermost begins / ends the pass (NOT reset with the rest)
+
+    def reset(self):
+        self.outs = {}              # (id(weight), first row) -> dict(weight, biases, M, N, segs, rows): queue_wgrad
+        self.ext = []               # foreign slab stacks: queue_slab_reduce
+        self.armed = False          # flush_queued_wgrads is queued as end-of-backward callback of the running backward
+        # _hip.riders_context(), given to every weight-gradient batch and GRU backward launch of the pass (rider batches wait in it)
+        self.riders = None
+        self.rider_keep = None      # (outs, launches) of the batch staged for the next GRU backward launch
+        self.rider_held = []        # ... of the batches whose slabs a reduction launch has yet to take in
+        self.held = []              # ... of the side-stream batches in flight: the main stream has yet to wait for them
+        self.fold = []              # fold-back terms, in registration order
+        self.drop_addends()
+    __init__ = reset                # (a new pass is a reset one)
+
+    def drop_addends(self):
+        """Forget addends (and the callback flag) left behind by a backward pass that raised before its end-of-backward callback
+        ran; without this every later pass would see a non-empty list, queue no callback and silently lose its addends."""
+        self.addends = []           # (parameter, tensor, event recorded on the producing stream)
+        self.addends_armed = False  # apply_grad_addends is queued as end-of-backward callback of the running backward
 
     def __enter__(self):
-        if _WGQ["scope"] == 0 and (_WGQ["outs"] or _WGQ["ext"] or _WGQ["armed"]):
-            _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False        # stale entries of a backward that raised
-        if _WGQ["scope"] == 0:
-            drop_grad_addends()                                             # (same: its callback never ran)
-            del _FOLD[:]
-            _WGQ["riders"], _WGQ["rider_keep"], _WGQ["rider_held"] = _hip.riders_context(), None, []
-        _WGQ["scope"] += 1
+        if self.depth == 0:
+            self.reset()            # (whatever a backward that raised outside a scope left behind: its callbacks never ran)
+            self.riders = _hip.riders_context()
+        self.depth += 1
         return self
 
     def __exit__(self, exc_type, exc, tb):
-        _WGQ["scope"] -= 1
-        if _WGQ["scope"] == 0:
-            if exc_type is None:
-                if _WGQ["outs"] or _WGQ["ext"]:
-                    flush_queued_wgrads()                  # a backward driven without the engine callback
-                _drain_riders()
-                _run_fold_back()
-            else:
-                _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False    # the callback never ran: drop the half-built batch
-                drop_grad_addends()
-                del _FOLD[:]
-                _drain_riders(discard=True)
-            _WGQ["riders"] = None
-            _join_side()
-        return False
+        self.depth -= 1
+        if self.depth == 0:
+            try:
+                if exc_type is None:
+                    flush_queued_wgrads()               # what the end-of-backward callback did not (normally: nothing is left)
+                else:
+                    self.drain_riders(discard=True)     # the callback never ran: the half-built batch is dropped below
+                    self.join_side()
+            finally:
+                self.reset()
+
+    def join_side(self):
+        """The main stream waits for the side-stream batch (if one is in flight); its operands may be released afterwards."""
+        if self.held:
+            torch.cuda.current_stream().wait_stream(_side_stream)
+            self.held = []
+
+    def drain_riders(self, discard=False):
+        """End of the backward pass: the rider batches' slab stacks that no reduction launch took in are reduced now."""
+        if self.rider_held or self.rider_keep:
+            if self.rider_keep and not discard:
+                finish_riders()
+            try:
+                _hip.call("mmdfn_wgrad_riders_drain", self.riders, _hip.stream(), 1 if discard else 0)
+            finally:
+                self.rider_held, self.rider_keep = [], None
+
+    def arm(self):                  # queue the end-of-backward flush, once per backward (the engine takes it only while one runs)
+        if not self.armed:
+            self.armed = True
+            torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
+
+    def take(self, ext=True):       # hands over what is queued so far ('armed' stays: the callback still runs for what follows)
+        outs, self.outs = list(self.outs.values()), {}
+        stacks, self.ext = (self.ext, []) if ext else ([], self.ext)
+        return outs, stacks
+
+
+_PASS = _BackwardPass()
+drop_grad_addends = _PASS.drop_addends
+
+
+def wgrad_batch():
+    """``with ops.wgrad_batch(): loss.backward()`` -- weight gradients of leaf parameters are batched into one launch pair
+    and written to ``.grad`` directly (see the comment above).  Re-entrant; exception-safe."""
+    return _PASS
 
 
 def wgrad_batching():
-    return _WGQ["scope"] > 0
+    return _PASS.depth > 0
 
 
 def _leaf(p):
@@ -169,7 +216,7 @@ def _hooked(p):
 
 
 def _queueable(weight, biases, M, N):
-    return (_WGQ["scope"] > 0 and _leaf(weight) and all(_leaf(b) for b in biases) and gemm_tn_supported(M, N)
+    return (_PASS.depth > 0 and _leaf(weight) and all(_leaf(b) for b in biases) and gemm_tn_supported(M, N)
             and len(biases) <= 2 and not _hooked(weight) and not any(_hooked(b) for b in biases))
 
 
@@ -178,16 +225,16 @@ def queue_wgrad(A, B, weight, biases=(), shift=0, rows=None):
     ``rows = (r0, r1)``: the contraction fills rows r0..r1-1 of weight.grad only (GraphConvolution.weight takes its two
     halves from hi^T dP and h0^T dP, the concatenated operand [hi | h0] never exists).
     Only valid inside a backward pass under ``wgrad_batch()`` (the flush is an end-of-backward callback)."""
-    if _WGQ["scope"] <= 0:
+    if _PASS.depth <= 0:
         raise RuntimeError("queue_wgrad outside a wgrad_batch() scope")
     A = _strided_rows(A)
     B = _strided_rows(B)
     r0, r1 = rows if rows is not None else (0, weight.shape[0])
     key = (id(weight), r0)
-    out = _WGQ["outs"].get(key)
+    out = _PASS.outs.get(key)
     if out is None:
         out = dict(weight=weight, biases=[], M=A.shape[1], N=B.shape[1], segs=[], rows=(r0, r1))
-        _WGQ["outs"][key] = out
+        _PASS.outs[key] = out
     for b in biases:
         if all(b is not x for x in out["biases"]):
             out["biases"].append(b)
@@ -196,9 +243,7 @@ def queue_wgrad(A, B, weight, biases=(), shift=0, rows=None):
             or (rows is not None and biases)):
         raise RuntimeError("queue_wgrad: inconsistent contributions to one parameter")
     out["segs"].append((A, B, int(shift)))
-    if not _WGQ["armed"]:
-        _WGQ["armed"] = True
-        torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
+    _PASS.arm()
 
 
 SLAB_RIDE = __import__("os").environ.get("MMDFN_SLAB_RIDE", "1") == "1"      # (0: A/B aid, the stacks get their own launches)
@@ -208,22 +253,21 @@ def slab_reduce_queueable(weight, biases):
     """May the slab stacks of ``weight`` / ``biases`` (partial sums another kernel wrote) be summed by the end-of-backward
     reduction launch instead of a launch of their own?  Same rules as queue_wgrad."""
     ps = ([weight] if weight is not None else []) + list(biases)
-    return SLAB_RIDE and _WGQ["scope"] > 0 and bool(ps) and all(_leaf(p) and not _hooked(p) for p in ps)
+    return SLAB_RIDE and _PASS.depth > 0 and bool(ps) and all(_leaf(p) and not _hooked(p) for p in ps)
 
 
-def queue_slab_reduce(part, colpart, splits, M, N, weight=None, biases=()):
+def queue_slab_reduce(part, colpart, splits, M, N, weight=None, biases=(), acc=None):
     """weight.grad (M, N) += sum of the ``splits`` slabs of ``part`` ([splits][M][N]); b.grad (M) += sum of the slabs of
     ``colpart`` ([splits][M]) for the ONE bias in ``biases`` -- summed by the reduction launch of the backward pass's
-    weight-gradient batch (mmdfn_gemm_tn_batch_ext).  Only inside a backward pass under ``wgrad_batch()``."""
-    if _WGQ["scope"] <= 0:
+    weight-gradient batch (mmdfn_gemm_tn_batch_ext), which adds to the destinations (``acc`` = 1), writes them (0) or adds where a
+    ``.grad`` exists by then (None).  Only inside a backward pass under ``wgrad_batch()``."""
+    if _PASS.depth <= 0:
         raise RuntimeError("queue_slab_reduce outside a wgrad_batch() scope")
     if len(biases) > 1 or (weight is None) != (part is None) or (colpart is None) != (len(biases) == 0):
         raise RuntimeError("queue_slab_reduce: one weight and / or one bias per slab stack")
-    _WGQ["ext"].append(dict(part=part, colpart=colpart, splits=int(splits), M=int(M), N=int(N) if weight is not None else 0,
-                            weight=weight, bias=biases[0] if biases else None))
-    if not _WGQ["armed"]:
-        _WGQ["armed"] = True
-        torch.autograd.Variable._execution_engine.queue_callback(flush_queued_wgrads)
+    _PASS.ext.append(dict(part=part, colpart=colpart, splits=int(splits), M=int(M), N=int(N) if weight is not None else 0,
+                          weight=weight, bias=biases[0] if biases else None, acc=acc))
+    _PASS.arm()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -232,8 +276,7 @@ def queue_slab_reduce(part, colpart, splits, M, N, weight=None, biases=()):
 # stand-ins instead of dG^T X_m and launches no dX product; one grouped launch behind the end-of-backward reduction derives
 # dW_ih, dW_m and db_m from them and writes (or accumulates into) the parameters' .grad.
 # ---------------------------------------------------------------------------------------------------
-_FOLD = []              # terms registered by the running backward pass, in registration order
-_FOLD_TICKETS = {}      # device -> the fold-back launch's zeroed ticket words (every launch leaves them zero)
+_FOLD_TICKETS = {}      # device -> the fold-back launch's zeroed ticket words (every launch leaves them zero): per process
 
 
 class _Workspace:
@@ -249,7 +292,7 @@ class _Workspace:
 
 def fold_back_queueable(params):
     """May the gradients of ``params`` (None entries ignored) be written by the fold-back launch?  Same rules as queue_wgrad."""
-    return _WGQ["scope"] > 0 and all(_leaf(p) and not _hooked(p) for p in params if p is not None)
+    return _PASS.depth > 0 and all(_leaf(p) and not _hooked(p) for p in params if p is not None)
 
 
 def queue_fold_back(A, u, w_ih, p_ih, W_m, b_m, bias=None):
@@ -261,7 +304,7 @@ def queue_fold_back(A, u, w_ih, p_ih, W_m, b_m, bias=None):
     n, D = A.shape[1], u.shape[1]
     Mh, ch = _Workspace((n, D), A.device), _Workspace((n,), A.device)
     queue_wgrad(A, u, Mh, ([bias] if bias is not None else []) + [ch])
-    _FOLD.append(dict(M=Mh, c=ch, wih=w_ih, p=p_ih, wm=W_m, bm=b_m))
+    _PASS.fold.append(dict(M=Mh, c=ch, wih=w_ih, p=p_ih, wm=W_m, bm=b_m))
 
 
 def _fold_tickets(dev):
@@ -276,10 +319,9 @@ def _fold_tickets(dev):
 
 def _run_fold_back():
     """The fold-back launch of the terms registered by this backward pass (behind every reduction of the batch)."""
-    if not _FOLD:
+    terms, _PASS.fold = _PASS.fold, []
+    if not terms:
         return
-    terms = list(_FOLD)
-    del _FOLD[:]
     dev = terms[0]["M"].grad.device
     seen = {}
 
@@ -324,30 +366,19 @@ def _run_fold_back():
             seen[k] = 1
 
 
-def _join_side():
-    """The main stream waits for the side-stream batch (if one is in flight); its operands may be released afterwards."""
-    if _WGQ["pending_join"]:
-        torch.cuda.current_stream().wait_stream(_WGQ["side"])
-        _WGQ["pending_join"] = False
-    _WGQ["held"] = []
-
-
-_GRAPH_DONE_HOOK = [None]
-
-
 def set_graph_backward_done_hook(fn):
     """``fn()`` is called ONCE where the graph part of the next backward pass ends (the adjacency builder's backward: the
     graph stack's, the fusion modules' and the head's gradients are complete, the encoders' nodes follow).  A two-part
-    gradient bucket (distributed.GradientBucket(parts=2)) starts its first all-reduce there."""
-    _GRAPH_DONE_HOOK[0] = fn
+    gradient bucket (distributed.GradientBucket(parts=2)) starts its first all-reduce there; it sets the hook BEFORE train.backward
+    opens the scope (so this is no state of the pass) and takes it back itself (``fn`` = None)."""
+    global _graph_done_hook
+    _graph_done_hook = fn
 
 
 def flush_queued_wgrads_now():
     """Issue the weight gradients queued so far on the current stream (the end-of-backward callback flushes the rest)."""
-    if _WGQ["outs"] or _WGQ["ext"]:
-        outs, ext = list(_WGQ["outs"].values()), _WGQ["ext"]
-        _WGQ["outs"], _WGQ["ext"] = {}, []   # 'armed' stays set: the end-of-backward callback still runs for the rest
-        _flush_outs(outs, None, ext)
+    if _PASS.outs or _PASS.ext:
+        _flush_outs(*_PASS.take())
 
 
 # what a CU delivers on the bf16-piece weight-gradient tiles (the cfg2 batch: 10.4 GFLOP in 96 us on 256 CUs) and what a
@@ -363,8 +394,8 @@ def stage_riders(rows, T):
     most 16 segments) as the CUs it leaves idle can finish while it runs; the rest stays queued for the next launch / the
     end-of-backward flush.  Returns the rider context to give that launch (None outside a ``wgrad_batch`` scope);
     ``finish_riders()`` must follow the launch."""
-    riders = _WGQ["riders"]
-    if not (RIDERS and _WGQ["scope"] > 0 and _WGQ["outs"]) or _WGQ["rider_keep"]:
+    riders = _PASS.riders
+    if not (RIDERS and _PASS.depth > 0 and _PASS.outs) or _PASS.rider_keep:
         return riders
     idle = _hip.query("mmdfn_gru_seq_bwd_idle_cus", len(rows), _hip.int_array(rows))
     if idle <= 0:
@@ -372,7 +403,7 @@ def stage_riders(rows, T):
     step_s = 1e-9 * _hip.query("mmdfn_gru_seq_bwd_step_ns", len(rows), _hip.int_array(rows))     # (0.65 us; the MFMA form 2.3)
     budget = RIDER_BUDGET * idle * max(T) * step_s * _RIDER_FLOPS_PER_CU_S
     take, nseg, work = [], 0, 0.0
-    for key, o in list(_WGQ["outs"].items()):
+    for key, o in list(_PASS.outs.items()):
         f = sum(2.0 * a.shape[0] * o["M"] * o["N"] for a, _, _ in o["segs"])
         if nseg + len(o["segs"]) > _RIDER_MAXSEG or work + f > 1.1 * budget:
             continue
@@ -382,34 +413,23 @@ def stage_riders(rows, T):
     if RIDER_LOG is not None:
         RIDER_LOG.append(dict(idle=idle, T=max(T), budget_gflop=budget / 1e9, taken_gflop=work / 1e9, taken_segments=nseg,
                               queued=[(o["M"], o["N"], len(o["segs"]), sum(a.shape[0] for a, _, _ in o["segs"]), k in take)
-                                      for k, o in _WGQ["outs"].items()]))
+                                      for k, o in _PASS.outs.items()]))
     if take:
-        outs = [_WGQ["outs"].pop(k) for k in take]      # 'armed' stays set: the end-of-backward callback flushes the rest
-        _flush_outs(outs, None, (), stage=True)
+        outs = [_PASS.outs.pop(k) for k in take]        # 'armed' stays set: the end-of-backward callback flushes the rest
+        _flush_outs(outs, stage=True)
     return riders
 
 
 def finish_riders():
     """Behind the GRU backward launch: a staged batch the launch did not take (another kernel form) is issued now; the
     references that kept its operands and slabs alive are dropped (the launches are in the stream)."""
-    if _WGQ["rider_keep"]:
+    if _PASS.rider_keep:
         try:
-            _hip.call("mmdfn_wgrad_riders_flush", _WGQ["riders"], _hip.stream())
+            _hip.call("mmdfn_wgrad_riders_flush", _PASS.riders, _hip.stream())
         finally:
             # the slabs are read again by the reduction launch that takes them in (the end-of-backward batch's): held until then
-            _WGQ["rider_held"].append(_WGQ["rider_keep"])
-            _WGQ["rider_keep"] = None
-
-
-def _drain_riders(discard=False):
-    """End of the backward pass: the rider batches' slab stacks that no reduction launch took in are reduced now."""
-    if _WGQ["rider_held"] or _WGQ["rider_keep"]:
-        if _WGQ["rider_keep"] and not discard:
-            finish_riders()
-        try:
-            _hip.call("mmdfn_wgrad_riders_drain", _WGQ["riders"], _hip.stream(), 1 if discard else 0)
-        finally:
-            _WGQ["rider_held"], _WGQ["rider_keep"] = [], None
+            _PASS.rider_held.append(_PASS.rider_keep)
+            _PASS.rider_keep = None
 
 
 def flush_queued_wgrads_early():
@@ -417,28 +437,16 @@ def flush_queued_wgrads_early():
     leaves NOW on a side stream, concurrently with the encoder backward that follows on the main stream.  Gradient
     buffers and the workspace are allocated on the main stream (the caching allocator's stream of record), the operands
     stay referenced until the main stream has waited for the side stream (end-of-backward callback)."""
-    hook = _GRAPH_DONE_HOOK[0]
-    if hook is not None:
-        hook()                               # (a two-part bucket: flushes what is queued and starts its first collective)
+    global _side_stream
+    if _graph_done_hook is not None:
+        _graph_done_hook()                   # (a two-part bucket: flushes what is queued and starts its first collective)
         return
-    if not (EARLY_WGRAD and _WGQ["scope"] > 0 and _WGQ["outs"]):
+    if not (EARLY_WGRAD and _PASS.depth > 0 and _PASS.outs):
         return
-    outs = list(_WGQ["outs"].values())
-    _WGQ["outs"] = {}                        # 'armed' stays: the end-of-backward callback flushes the rest and joins
-    if _WGQ["side"] is None:
-        _WGQ["side"] = torch.cuda.Stream()
-    _flush_outs(outs, _WGQ["side"])
-
-
-_GRAD_ADDENDS = []      # (parameter, tensor, event recorded on the producing stream)
-_GRAD_ADDENDS_ARMED = [False]    # the end-of-backward callback of the RUNNING backward pass has been queued
-
-
-def drop_grad_addends():
-    """Forget addends (and the callback flag) left behind by a backward pass that raised before its end-of-backward callback
-    ran; without this every later pass would see a non-empty list, queue no callback and silently lose its addends."""
-    del _GRAD_ADDENDS[:]
-    _GRAD_ADDENDS_ARMED[0] = False
+    if _side_stream is None:
+        _side_stream = torch.cuda.Stream()
+    outs, _ = _PASS.take(ext=False)          # (the slab stacks wait for the end-of-backward callback, which also joins)
+    _flush_outs(outs, side=_side_stream)
 
 
 def add_grad_addends(pairs):
@@ -449,18 +457,17 @@ def add_grad_addends(pairs):
     ev.record(torch.cuda.current_stream())
     for prm, t in pairs:
         if prm.requires_grad:
-            _GRAD_ADDENDS.append((prm, t, ev))
-    if _GRAD_ADDENDS and not _GRAD_ADDENDS_ARMED[0]:
-        _GRAD_ADDENDS_ARMED[0] = True
+            _PASS.addends.append((prm, t, ev))
+    if _PASS.addends and not _PASS.addends_armed:
+        _PASS.addends_armed = True
         torch.autograd.Variable._execution_engine.queue_callback(apply_grad_addends)
 
 
 def apply_grad_addends():
-    _GRAD_ADDENDS_ARMED[0] = False
-    if not _GRAD_ADDENDS:
+    items = _PASS.addends
+    _PASS.drop_addends()
+    if not items:
         return
-    items = list(_GRAD_ADDENDS)
-    del _GRAD_ADDENDS[:]
     cur = torch.cuda.current_stream()
     seen = set()
     for _, t, ev in items:
@@ -481,12 +488,12 @@ def apply_grad_addends():
 
 def flush_queued_wgrads():
     """Issue every queued weight-gradient contraction (one launch pair per <= 40 segments) into the .grad fields."""
-    outs, ext = list(_WGQ["outs"].values()), _WGQ["ext"]
-    _WGQ["outs"], _WGQ["ext"], _WGQ["armed"] = {}, [], False
-    _join_side()             # first: a parameter may collect contributions from both batches (the later one accumulates)
+    outs, ext = _PASS.take()
+    _PASS.armed = False      # (this IS the callback, or stands in for it: the next contribution queues it again)
+    _PASS.join_side()        # first: a parameter may collect contributions from both batches (the later one accumulates)
     if outs or ext:
-        _flush_outs(outs, None, ext)
-    _drain_riders()
+        _flush_outs(outs, ext)
+    _PASS.drain_riders()
     _run_fold_back()         # behind every reduction launch: M and c are complete
 
 
@@ -512,9 +519,9 @@ def _ext_destinations(ext):
     return items
 
 
-def _flush_outs(outs, side, ext=(), stage=False):
+def _flush_outs(outs, ext=(), side=None, stage=False):
     ext_items = _ext_destinations(ext) if ext else []
-    riders = _WGQ["riders"]
+    riders = _PASS.riders
     if not outs:
         _prepare_wgrad_batch([], ext_items, riders=riders)(_hip.stream())
         return
@@ -581,20 +588,19 @@ def _flush_outs(outs, side, ext=(), stage=False):
                                      riders=riders)
                 for b in batches]          # allocations (workspace) on the current stream
     if stage:
-        _WGQ["rider_keep"] = (outs, prepared)
+        _PASS.rider_keep = (outs, prepared)
     if ext_items and not ride:
         _prepare_wgrad_batch([], ext_items, riders=riders)(_hip.stream())
     if side is not None:
         side.wait_stream(torch.cuda.current_stream())             # operands, zero fills and allocations are ordered before
-        _WGQ["held"].append((outs, prepared))
-        _WGQ["pending_join"] = True
+        _PASS.held.append((outs, prepared))
     stream = _hip.stream() if side is None else ctypes.c_void_p(side.cuda_stream)
     for call in prepared:
         call(stream)
 
 
 def _launch_wgrad_batch(batch):
-    _prepare_wgrad_batch(batch, riders=_WGQ["riders"])(_hip.stream())
+    _prepare_wgrad_batch(batch, riders=_PASS.riders)(_hip.stream())
 
 
 def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
@@ -653,14 +659,8 @@ def _prepare_wgrad_batch(batch, ext_items=None, stage=False, riders=None):
 def join_weight_grads():
     """Kept for callers of earlier versions: the queue is flushed by the end-of-backward callback (or by the exit of the
     ``wgrad_batch()`` scope); anything still queued here is issued now."""
-    if _WGQ["outs"] and _WGQ["scope"] == 0:
+    if _PASS.outs and _PASS.depth == 0:
         flush_queued_wgrads()
-
-
-def set_async_weight_grads(flag):
-    """Removed option (side-stream weight gradients measured slower on MI355X, profiles/r01_propagate_tuning.md)."""
-    if flag:
-        raise NotImplementedError("side-stream weight gradients were removed: they are batched into one launch now")
 
 
 def _wgrad_inline(dy2, x2, want_b):

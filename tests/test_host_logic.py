@@ -364,13 +364,129 @@ def test_grad_addends_of_a_backward_that_raised_do_not_block_later_passes():
     'callback queued' state behind (later passes would silently drop their addends)."""
     from mm_dfn_amd import ops
     p = torch.nn.Parameter(torch.zeros(3))
-    ops._GRAD_ADDENDS.append((p, torch.ones(3), None))      # what a failed pass leaves behind
-    ops._GRAD_ADDENDS_ARMED[0] = True
+    ops._PASS.addends.append((p, torch.ones(3), None))      # what a failed pass leaves behind
+    ops._PASS.addends_armed = True
     with ops.wgrad_batch():
-        assert not ops._GRAD_ADDENDS and not ops._GRAD_ADDENDS_ARMED[0]
+        assert not ops._PASS.addends and not ops._PASS.addends_armed
     with pytest.raises(ZeroDivisionError):
         with ops.wgrad_batch():
-            ops._GRAD_ADDENDS.append((p, torch.ones(3), None))
-            ops._GRAD_ADDENDS_ARMED[0] = True
+            ops._PASS.addends.append((p, torch.ones(3), None))
+            ops._PASS.addends_armed = True
             1 / 0
-    assert not ops._GRAD_ADDENDS and not ops._GRAD_ADDENDS_ARMED[0]
+    assert not ops._PASS.addends and not ops._PASS.addends_armed
+
+
+def _pass_is_clean(ps):
+    """Every per-pass field of the weight-gradient queue's pass object is empty (the scope depth is not one of them)."""
+    return (not ps.outs and not ps.ext and not ps.armed and ps.riders is None and ps.rider_keep is None and not ps.rider_held
+            and not ps.held and not ps.fold and not ps.addends and not ps.addends_armed)
+
+
+class _InBackward(torch.autograd.Function):
+    """Identity whose backward runs ``fn()``: the queue can only be filled while a backward pass is running (its flush is an
+    end-of-backward callback of the autograd engine)."""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.fn()
+        return g, None
+
+
+class _Stop(Exception):
+    pass
+
+
+def _queue_one_of_each(w, b):
+    """A queue_wgrad contribution, a queue_slab_reduce entry and a queue_fold_back term, on CPU tensors (nothing is launched)."""
+    from mm_dfn_amd import ops
+    ops.queue_wgrad(torch.zeros(5, 8), torch.zeros(5, 4), w)
+    ops.queue_slab_reduce(None, torch.zeros(2, 8), 2, 8, 0, biases=[b])
+    ops.queue_fold_back(torch.zeros(5, 8), torch.zeros(5, 4), torch.zeros(8, 12), torch.nn.Parameter(torch.zeros(8, 12)),
+                        torch.nn.Parameter(torch.zeros(12, 4)), None)
+
+
+def test_a_scope_that_raises_leaves_a_clean_backward_pass():
+    """Whatever the nodes of a backward pass queued -- contributions, foreign slab stacks, fold-back terms, with the callback
+    armed -- is gone when the pass raises, and the next scope starts from a clean pass (nothing is flushed: the tensors are CPU
+    tensors, a launch would raise)."""
+    from mm_dfn_amd import ops
+    w, b = torch.nn.Parameter(torch.zeros(8, 4)), torch.nn.Parameter(torch.zeros(8))
+    seen = []
+
+    def node():
+        _queue_one_of_each(w, b)
+        ps = ops._PASS
+        seen.append((len(ps.outs), len(ps.ext), len(ps.fold), ps.armed, ps.depth, ps.riders is not None))
+        raise _Stop()
+
+    x = torch.zeros(2, requires_grad=True)
+    with pytest.raises(_Stop):
+        with ops.wgrad_batch():
+            _InBackward.apply(x, node).sum().backward()
+    assert seen == [(2, 1, 1, True, 1, True)]               # (the fold-back term queues its dG^T u contribution as well)
+    assert _pass_is_clean(ops._PASS) and ops._PASS.depth == 0 and not ops.wgrad_batching()
+    assert w.grad is None and b.grad is None
+    with ops.wgrad_batch():
+        assert ops._PASS.depth == 1 and ops._PASS.riders is not None
+        assert not ops._PASS.outs and not ops._PASS.ext and not ops._PASS.fold and not ops._PASS.armed
+    assert _pass_is_clean(ops._PASS) and ops._PASS.depth == 0
+
+
+def test_a_nested_scope_neither_resets_nor_flushes_the_outer_queue():
+    from mm_dfn_amd import ops
+    w, b = torch.nn.Parameter(torch.zeros(8, 4)), torch.nn.Parameter(torch.zeros(8))
+    seen = []
+
+    def node():
+        _queue_one_of_each(w, b)
+        ps = ops._PASS
+        def queued():
+            return (list(ps.outs), [len(o["segs"]) for o in ps.outs.values()], [id(e) for e in ps.ext], [id(t) for t in ps.fold],
+                    ps.armed, id(ps.riders))
+        before = queued()
+        with ops.wgrad_batch():
+            seen.append(ps.depth)
+            assert queued() == before                       # entering resets nothing
+        seen.append(ps.depth)
+        assert queued() == before                           # leaving flushes nothing
+        assert len(before[0]) == 2 and len(before[2]) == 1 and len(before[3]) == 1 and w.grad is None and b.grad is None
+        raise _Stop()                                       # (leaves the outer scope without a launch)
+
+    x = torch.zeros(2, requires_grad=True)
+    with pytest.raises(_Stop):
+        with ops.wgrad_batch():
+            _InBackward.apply(x, node).sum().backward()
+    assert seen == [2, 1] and ops._PASS.depth == 0
+
+
+def test_queueing_outside_a_scope_raises():
+    from mm_dfn_amd import ops
+    w, b = torch.nn.Parameter(torch.zeros(8, 4)), torch.nn.Parameter(torch.zeros(8))
+    assert not ops.wgrad_batching()
+    with pytest.raises(RuntimeError, match="outside a wgrad_batch"):
+        ops.queue_wgrad(torch.zeros(5, 8), torch.zeros(5, 4), w)
+    with pytest.raises(RuntimeError, match="outside a wgrad_batch"):
+        ops.queue_slab_reduce(None, torch.zeros(2, 8), 2, 8, 0, biases=[b])
+    assert _pass_is_clean(ops._PASS)
+
+
+def test_graph_done_hook_set_before_the_scope_survives_entering_it():
+    """distributed.GradientBucket.arm() sets the hook BEFORE train.backward opens the scope: the fresh pass that the scope starts
+    from must not take it away (the bucket's first all-reduce would silently never start)."""
+    from mm_dfn_amd import ops, ops_wgrad
+    calls = []
+    ops.set_graph_backward_done_hook(lambda: calls.append(ops._PASS.depth))
+    try:
+        with ops.wgrad_batch():
+            assert ops_wgrad._graph_done_hook is not None
+            ops.flush_queued_wgrads_early()                 # (where the graph part of a backward pass ends)
+        assert calls == [1]
+        assert ops_wgrad._graph_done_hook is not None       # taking it back is the hook's own business (GradientBucket.early_part)
+    finally:
+        ops.set_graph_backward_done_hook(None)
+    assert ops_wgrad._graph_done_hook is None

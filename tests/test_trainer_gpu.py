@@ -464,7 +464,7 @@ def test_weight_gradient_batch_is_opt_in_and_matches_plain_autograd():
     logp = m(x, b["qmask"], b["umask"], b["lengths"], b["acouf"], b["visuf"])[0]
     (gx,) = torch.autograd.grad(logp.sum(), [x])
     assert gx is not None and all(p.grad is None for p in m.parameters())
-    assert not ops._WGQ["outs"] and not ops._WGQ["armed"]
+    assert not ops._PASS.outs and not ops._PASS.armed
 
 
 def test_slab_stacks_of_the_head_and_the_gather_bias_ride_on_the_batch_reduction():
@@ -507,7 +507,7 @@ def test_slab_stacks_of_the_head_and_the_gather_bias_ride_on_the_batch_reduction
     names = [e.key for e in prof.key_averages()]
     assert any("head_bwd_kernel" in n for n in names) and any("gemm_tn_batch_reduce" in n for n in names), names
     assert not [n for n in names if "head_reduce" in n or "colsum_final" in n], names
-    assert not ops._WGQ["outs"] and not ops._WGQ["ext"] and not ops._WGQ["armed"]
+    assert not ops._PASS.outs and not ops._PASS.ext and not ops._PASS.armed
 
 
 def test_parameter_hooks_fire_under_the_weight_gradient_batch():
@@ -641,7 +641,7 @@ def test_weight_gradient_queue_survives_a_backward_that_raises():
     logp = m(Boom.apply(x), b["qmask"], b["umask"], b["lengths"], b["acouf"], b["visuf"])[0]
     with pytest.raises(RuntimeError, match="boom"):
         T.backward(FocalLoss(gamma=0.5)(logp, flat))
-    assert not ops._WGQ["outs"] and not ops._WGQ["armed"] and ops._WGQ["scope"] == 0
+    assert not ops._PASS.outs and not ops._PASS.armed and ops._PASS.depth == 0
     m.zero_grad(set_to_none=True)
     T.backward(_loss(m, b, flat))
     for n, p in m.named_parameters():
