@@ -22,8 +22,10 @@ ARCH = "gfx950"
 # kernels whose vector-memory requests are asm statements with hand-counted waits: a register spill between a request and its wait
 # would store a register the load has not written yet.  source file -> substrings of the mangled kernel names: the build fails
 # unless hipcc reports ScratchSize 0 for every such kernel.
-# (gru.hip: the direct backward recurrence, gru_bwd_direct_body, in the plain launch <8, 4, 0, 1> and in the rider launch)
-NO_SPILL = {"gru.hip": ("gru_seq_bwd_kpart_kernelILi8ELi4ELi0ELi1E", "gru_seq_bwd_riders_kernelILb1E")}
+# (gru.hip: the direct backward recurrence, gru_bwd_direct_body, in the plain launch <8, 4, 0, 1> and in the rider launch; the
+# direct forward recurrence, gru_fwd_direct_body, in the plain launch <0, 0, 0, 1> and in the flag-rider launch <1>)
+NO_SPILL = {"gru.hip": ("gru_seq_bwd_kpart_kernelILi8ELi4ELi0ELi1E", "gru_seq_bwd_riders_kernelILb1E",
+                        "gru_seq_fwd_io_kernelILi0ELi0ELi0ELi1E", "gru_seq_fwd_io_flags_kernelILi1E")}
 
 
 def sources():

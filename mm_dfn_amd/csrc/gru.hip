@@ -578,13 +578,16 @@ __global__ __launch_bounds__(NT) void gru_seq_fwd_kernel(FwdGroups G) {
 // of a double-buffered result array, one step's worth per step, and joins the same per-step barrier; the block boundary
 // needs no barrier of its own (the last step of a block writes its results before its barrier instead of after it).  A unit's
 // five results go to LDS as one 16-byte + one 4-byte write ([unit][8] layout) instead of five 4-byte writes.
+// Where it runs: the SEGMENTED launches (SEG = 1) with one chain per CU, and the tuning library's SCALAR_FMA / ABL instances.
+// The PLAIN launch (SEG = 0) runs gru_fwd_direct_body (below the backward kernels: four waves, no I/O wave, no staging);
+// this body stays its A/B partner and bit-for-bit test reference in the tuning library (MMDFN_GRU_FWD_STAGED=1).
 // =====================================================================================================
 // ABL (tuning build, timing only): 1 no matvec, 2 no transcendental gate math, 4 no result writes, 8 no h exchange wait
 // (the LDS write of h stays, the barrier goes), 16 no gate-operand reads
 // SEG = 1: segmented launch (see SegInfo): 1-D grid of chains, the time loop runs over the chain's flattened schedule
 // (S steps, each naming its row and t), the state is re-initialised at segment starts (one extra barrier there), and the
 // positions a truncated / silent row does not visit are filled afterwards (copies of the all-padding sequence, or zeros).
-// (the body of workgroup (bx, by) = (sequence slot, direction) of the plain launch; SEG launches decode their chain themselves)
+// (SEG = 0: the body of workgroup (bx, by) = (sequence slot, direction); SEG launches decode their chain themselves)
 template <int SCALAR_FMA, int ABL, int SEG>
 __device__ __forceinline__ void gru_fwd_io_body(const FwdGroups& G, const int bx, const int by) {
     constexpr int TB = 4;                          // steps per block
@@ -926,20 +929,37 @@ __device__ __forceinline__ void gru_fwd_io_body(const FwdGroups& G, const int bx
     }
 }
 
-template <int SCALAR_FMA, int ABL, int SEG>
-__global__ __launch_bounds__(320) void gru_seq_fwd_io_kernel(FwdGroups G) {
-    gru_fwd_io_body<SCALAR_FMA, ABL, SEG>(G, (int)blockIdx.x, (int)blockIdx.y);
+// the direct form of the plain recurrence on four waves (defined behind the request / wait helpers it shares with the backward one)
+__device__ __forceinline__ void gru_fwd_direct_body(const FwdGroups& G, const int bx, const int by);
+
+// DIRECT = 1 (SCALAR_FMA = ABL = SEG = 0 only): gru_fwd_direct_body on 256 threads, launched with FWD_DIRECT_LDS of dynamic LDS
+template <int SCALAR_FMA, int ABL, int SEG, int DIRECT = 0>
+__global__ __launch_bounds__(DIRECT ? NT : 320) void gru_seq_fwd_io_kernel(FwdGroups G) {
+    if constexpr (DIRECT) {
+        static_assert(SCALAR_FMA == 0 && ABL == 0 && SEG == 0, "the direct body is the plain recurrence");
+        gru_fwd_direct_body(G, (int)blockIdx.x, (int)blockIdx.y);
+    } else {
+        gru_fwd_io_body<SCALAR_FMA, ABL, SEG>(G, (int)blockIdx.x, (int)blockIdx.y);
+    }
 }
 
 // The plain forward launch WITH the step's dropout-flag draw aboard: workgroups [0, 2 x slots) run the recurrences, the
-// workgroups behind them (at most one per idle CU: the kernel's register budget keeps a CU to one workgroup) draw the keep flags
-// of the whole step (keep_flags_body.h) -- the flags' first consumer is the dropout BEHIND this recurrence (nn.GRU's
-// inter-layer dropout, reference model.py:866), so the generator launch that used to sit between the two GRU layers (7.7 us at
-// cfg2) is gone.  Same flags as the launch of its own: which counter yields which flag depends on neither the grid nor the block size.
-__global__ __launch_bounds__(320) void gru_seq_fwd_io_flags_kernel(const FwdGroups G, const kfb::FlagJob J, const int nslots) {
+// workgroups behind them (at most one per idle CU: the launch's LDS request -- the five-wave form's register budget -- keeps a CU
+// to one workgroup) draw the keep flags of the whole step (keep_flags_body.h) -- the flags' first consumer is the dropout BEHIND
+// this recurrence (nn.GRU's inter-layer dropout, reference model.py:866), so the generator launch that used to sit between the
+// two GRU layers (7.7 us at cfg2) is gone.  Same flags as the launch of its own: which counter yields which flag depends on
+// neither the grid nor the block size.  DIRECT = 1: the direct body on 256 threads; 0: the five-wave body on 320 (tuning library).
+template <int DIRECT>
+__global__ __launch_bounds__(DIRECT ? NT : 320) void gru_seq_fwd_io_flags_kernel(const FwdGroups G, const kfb::FlagJob J,
+                                                                              const int nslots) {
     const int bid = (int)blockIdx.x;
-    if (bid < 2 * nslots) gru_fwd_io_body<0, 0, 0>(G, bid % nslots, bid / nslots);
-    else kfb::keep_flags_block<320>(J, bid - 2 * nslots, (int)gridDim.x - 2 * nslots);
+    if constexpr (DIRECT) {
+        if (bid < 2 * nslots) gru_fwd_direct_body(G, bid % nslots, bid / nslots);
+        else kfb::keep_flags_block<NT>(J, bid - 2 * nslots, (int)gridDim.x - 2 * nslots);
+    } else {
+        if (bid < 2 * nslots) gru_fwd_io_body<0, 0, 0>(G, bid % nslots, bid / nslots);
+        else kfb::keep_flags_block<320>(J, bid - 2 * nslots, (int)gridDim.x - 2 * nslots);
+    }
 }
 
 // Backward through time.  dh_prev[u] = sum_j dgh[j] W_hh[j][u] + dh z: lane (u, half) keeps W_hh[j][u] for
@@ -1787,6 +1807,234 @@ __device__ __forceinline__ void gru_bwd_direct_body(const BwdGroups& G, const in
     static_while<0, D>(tail_step, T - T_trips);
 }
 
+// The DIRECT form of the plain (SEG = 0, one sequence per workgroup) FORWARD recurrence: the four recurrence waves of
+// gru_fwd_io_body<0, 0, 0> without its I/O wave.  A lane needs three floats of its own unit per step (gi_r, gi_z, gi_n) and the
+// pair's owner produces five (y | r, z, n, W_hn h + b_hn): every lane requests its operands of step s + FWD_RING_D straight from
+// global memory into a register ring and the results go straight to global memory at the end of the step.  No in_s / out_s /
+// scratch (832 bytes of LDS instead of 38 KB), no block loop, no `last` branch, no deferred result write, and the per-step
+// barrier has four waves, none of them late.  What is left on a wave's LDS queue per step is the 13 broadcast loads of h_{t-1}
+// (the three ds_read_b32 and the ds_write_b128 + ds_write_b32 that sat between them are gone: the lgkmcnt immediates behind the
+// last h load are 5 .. 0, were 10 .. 5) and the one write of h_t.
+// Lane mapping, weights, h exchange and arithmetic are those of the five-wave body: y and the gates are bit-identical.
+// Requests (GRU_VM_LOAD): a wave-uniform row base into gi, advanced by +-rows 6H floats per step and stopped at the last step
+// (later requests repeat its row and are never consumed), the lane's byte offset 4 uu, the planes literal offsets 400 / 800;
+// unconditional, never outside gi (lanes without a unit read unit GH - 1).  They are issued behind the first six h loads: the
+// vector-memory issue fills the LDS latency in front of the first FMA.
+// Results: FWD_PAIR_STORES = 1 pairs two gate planes into one fully active store (even lane r | odd lane z, even n | odd ghn:
+// both lanes of a pair hold all five values behind pair_swap) and the owners store y: S = 3 instructions; 0: five stores from
+// the owner lanes.  Gates nontemporal (the backward pass reads them), y temporal.  Every wave has owner lanes, so every store is
+// issued in every wave: the wait counts rely on it.
+// Waits: with L = 3 loads and S stores per step, step s consumes its operands behind s_waitcnt vmcnt((L + S) D), placed behind the
+// matvec (the L D loads requested since, the S D stores of the D steps before).  Whole trips of D + 1 steps on static slot
+// registers; in the FIRST trip only k steps have stored in front of position k: L D + S k, a copy of the trip with its own
+// immediates; tail step j, which requests nothing, waits with L (D - 1 - j) + S j (valid with and without a trip in front of it).
+// As in the backward body a slot is one "+v" chain, everything a store consumes is pinned in front of it, and build.py refuses
+// scratch (NO_SPILL).
+#ifndef MMDFN_FWD_RING_D
+#define MMDFN_FWD_RING_D BWD_RING_D
+#endif
+#ifndef MMDFN_FWD_PAIR_STORES
+#define MMDFN_FWD_PAIR_STORES 1
+#endif
+constexpr int FWD_RING_D = MMDFN_FWD_RING_D;
+constexpr int FWD_PAIR_STORES = MMDFN_FWD_PAIR_STORES;
+// what the launches request: more than half a CU's 160 KB -- one recurrence per CU, as the five-wave form's registers had it
+constexpr int FWD_DIRECT_LDS = BWD_DIRECT_LDS;
+
+template <int N>
+__device__ __forceinline__ void vm_wait3(float (&r)[3]) {
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]) : "n"(N));
+}
+#define GRU_VM_STORE(off, val, base, lit) \
+    asm volatile("global_store_dword %0, %1, %2" lit : : "v"(off), "v"(val), "s"(base) : "memory")
+
+__device__ __forceinline__ void gru_fwd_direct_body(const FwdGroups& G, const int bx, const int by) {
+    constexpr int D = FWD_RING_D, NS = D + 1;
+    constexpr int L = 3, S = FWD_PAIR_STORES ? 3 : 5;
+    static_assert(D >= 1 && (L + S) * D <= 63, "s_waitcnt vmcnt((L + S) D) must fit the 6-bit immediate");
+    __shared__ __attribute__((aligned(16))) float hs[2][GH + 4];
+
+    int gidx = 0;
+    while (gidx + 1 < G.n && bx >= G.slice0[gidx + 1]) ++gidx;
+    const int dir = by;
+    const int row = bx - G.slice0[gidx];
+    const int T = G.T[gidx];
+    const int rows = G.rows[gidx];
+    if (T <= 0) return;
+    // lane pair (2u, 2u+1) = hidden unit u x half of the contraction (lanes without a unit compute on unit GH-1 and store nothing)
+    const int tid = threadIdx.x;
+    const int u = tid >> 1;
+    const int half = tid & 1;
+    const bool active = u < GH;
+    const int uu = active ? u : GH - 1;
+    const int kbase = half ? KH0 : 0;
+    const int klen = half ? GH - KH0 : KH0;
+    const float* __restrict__ gi = G.gi[gidx];
+    const float* __restrict__ w_hh = G.w_hh[2 * gidx + dir];
+    const float* __restrict__ b_hh = G.b_hh[2 * gidx + dir];
+    float* __restrict__ y = G.y[gidx];
+    float* __restrict__ gates = G.gates[gidx];
+    f32x2 wr[KW / 2], wz[KW / 2], wn[KW / 2];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const bool ok = k < klen;
+        const int kk = kbase + (ok ? k : 0);
+        wr[k >> 1][k & 1] = ok ? w_hh[(int64_t)(0 * GH + uu) * GH + kk] : 0.f;
+        wz[k >> 1][k & 1] = ok ? w_hh[(int64_t)(1 * GH + uu) * GH + kk] : 0.f;
+        wn[k >> 1][k & 1] = ok ? w_hh[(int64_t)(2 * GH + uu) * GH + kk] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < KW / 2; ++k) {
+        pin_loaded(wr[k]);
+        pin_loaded(wz[k]);
+        pin_loaded(wn[k]);
+    }
+    float bhr = b_hh[uu], bhz = b_hh[GH + uu], bhn = b_hh[2 * GH + uu];
+    pin_loaded(bhr);
+    pin_loaded(bhz);
+    pin_loaded(bhn);
+    const bool mine = active && half == 0;
+    float hprev = 0.f;
+    for (int i = tid; i < 2 * (GH + 4); i += NT) (&hs[0][0])[i] = 0.f;
+    __syncthreads();
+
+    // Row bases (scalar registers), advanced by a constant stride per step: step s works on t = dir ? T-1-s : s
+    const int64_t dt = dir ? -1 : 1;
+    const int64_t o0 = (int64_t)(dir ? T - 1 : 0) * rows + row;
+    const int64_t st_i = dt * rows * (6 * GH), st_y = dt * rows * (2 * GH), st_g = dt * rows * (8 * GH);
+    const float* pi = gi + o0 * (6 * GH) + dir * 3 * GH;
+    float* py = y + o0 * (2 * GH) + dir * GH;
+    float* pg = gates + (o0 * 2 + dir) * (4 * GH);
+    uint32_t ioff = (uint32_t)uu * 4u;                                  // the lane's byte offsets: operands,
+    uint32_t yoff = (uint32_t)uu * 4u;                                  // y (owners),
+    uint32_t goff = (uint32_t)uu * 4u + (FWD_PAIR_STORES && half ? 4u * GH : 0u);      // gate planes
+    asm volatile("" : "+v"(ioff), "+v"(yoff), "+v"(goff));
+    int f = 0;
+    // the three operands of the next step not requested yet
+    auto fetch = [&](float (&o3)[3]) {
+        GRU_VM_LOAD(o3[0], ioff, pi, "");
+        GRU_VM_LOAD(o3[1], ioff, pi, " offset:400");
+        GRU_VM_LOAD(o3[2], ioff, pi, " offset:800");
+        pi += (f + 1 < T) ? st_i : 0;
+        ++f;
+    };
+
+    float ring[NS][3];
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) ring[k][e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(ring[k]);
+
+    // one step: operands in iv behind s_waitcnt vmcnt(NC); REQ: the step requests into nx behind its first six h loads
+    auto run_step = [&](auto NC, auto REQ, const int step, float (&iv)[3], float (&nx)[3]) {
+        const int cur = step & 1;
+        // LDS operations of the step in ISSUE order: the 13 broadcast loads of h_{t-1} through a ring of six float4 registers,
+        // six groups ahead of their FMAs, and nothing else (a wave's LDS operations execute in order); all from inline asm, so
+        // the hand-counted lgkmcnt waits are exact
+        f32x2 ar0 = {0.f, 0.f}, az0 = {0.f, 0.f}, an0 = {0.f, 0.f}, ar1 = {0.f, 0.f}, az1 = {0.f, 0.f}, an1 = {0.f, 0.f};
+        constexpr int HLOOK = 6;
+        const uint32_t haddr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const float*)(&hs[cur][kbase]));
+        f32x4 hb[HLOOK];
+#define GRU_LDS_RD(J)                                                                                        \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(hb[(J) % HLOOK]) : "v"(haddr), "i"(16 * (J)) : "memory")
+#define GRU_LDS_WAIT(N, J) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(hb[(J) % HLOOK]) : : "memory")
+#define GRU_GROUP(K4)                                                                                        \
+    do {                                                                                                     \
+        const f32x4 h4 = hb[(K4) % HLOOK];                                                                   \
+        const f32x2 ha = {h4.x, h4.y}, hb2 = {h4.z, h4.w};                                                   \
+        ar0 = __builtin_elementwise_fma(wr[2 * (K4)], ha, ar0);                                              \
+        az0 = __builtin_elementwise_fma(wz[2 * (K4)], ha, az0);                                              \
+        an0 = __builtin_elementwise_fma(wn[2 * (K4)], ha, an0);                                              \
+        ar1 = __builtin_elementwise_fma(wr[2 * (K4) + 1], hb2, ar1);                                         \
+        az1 = __builtin_elementwise_fma(wz[2 * (K4) + 1], hb2, az1);                                         \
+        an1 = __builtin_elementwise_fma(wn[2 * (K4) + 1], hb2, an1);                                         \
+    } while (0)
+        GRU_LDS_RD(0); GRU_LDS_RD(1); GRU_LDS_RD(2); GRU_LDS_RD(3); GRU_LDS_RD(4); GRU_LDS_RD(5);
+        if constexpr (decltype(REQ)::value) fetch(nx);
+        GRU_LDS_WAIT(5, 0); GRU_GROUP(0); GRU_LDS_RD(6);
+        GRU_LDS_WAIT(5, 1); GRU_GROUP(1); GRU_LDS_RD(7);
+        GRU_LDS_WAIT(5, 2); GRU_GROUP(2); GRU_LDS_RD(8);
+        GRU_LDS_WAIT(5, 3); GRU_GROUP(3); GRU_LDS_RD(9);
+        GRU_LDS_WAIT(5, 4); GRU_GROUP(4); GRU_LDS_RD(10);
+        GRU_LDS_WAIT(5, 5); GRU_GROUP(5); GRU_LDS_RD(11);
+        GRU_LDS_WAIT(5, 6); GRU_GROUP(6); GRU_LDS_RD(12);
+        GRU_LDS_WAIT(5, 7); GRU_GROUP(7);
+        GRU_LDS_WAIT(4, 8); GRU_GROUP(8);
+        GRU_LDS_WAIT(3, 9); GRU_GROUP(9);
+        GRU_LDS_WAIT(2, 10); GRU_GROUP(10);
+        GRU_LDS_WAIT(1, 11); GRU_GROUP(11);
+        GRU_LDS_WAIT(0, 12); GRU_GROUP(12);
+#undef GRU_GROUP
+#undef GRU_LDS_WAIT
+#undef GRU_LDS_RD
+        float ar = (ar0.x + ar0.y) + (ar1.x + ar1.y);
+        float az = (az0.x + az0.y) + (az1.x + az1.y);
+        float an = (an0.x + an0.y) + (an1.x + an1.y);
+        ar += pair_swap(ar);
+        az += pair_swap(az);
+        an += pair_swap(an);
+        vm_wait3<decltype(NC)::value>(iv);
+        const float g0 = iv[0], g1 = iv[1], g2 = iv[2];
+        float ghn = an + bhn;
+        float rr = sigmoidf_(g0 + ar + bhr);
+        float zz = sigmoidf_(g1 + az + bhz);
+        float nn = tanhf_(g2 + rr * ghn);
+        float hnew = (1.0f - zz) * nn + zz * hprev;
+        if (mine) hs[cur ^ 1][u] = hnew;
+        // (everything the stores read is final HERE: the slot is requested again in the next step)
+        asm volatile("" : "+v"(hnew), "+v"(rr), "+v"(zz), "+v"(nn), "+v"(ghn));
+        hprev = hnew;
+        if constexpr (FWD_PAIR_STORES) {
+            const float va = half ? zz : rr, vb = half ? ghn : nn;
+            if (active) {
+                GRU_VM_STORE(goff, va, pg, " nt");
+                GRU_VM_STORE(goff, vb, pg, " offset:800 nt");
+                if (mine) GRU_VM_STORE(yoff, hnew, py, "");
+            }
+        } else {
+            if (mine) {
+                GRU_VM_STORE(yoff, hnew, py, "");
+                GRU_VM_STORE(goff, rr, pg, " nt");
+                GRU_VM_STORE(goff, zz, pg, " offset:400 nt");
+                GRU_VM_STORE(goff, nn, pg, " offset:800 nt");
+                GRU_VM_STORE(goff, ghn, pg, " offset:1200 nt");
+            }
+        }
+        py += st_y;
+        pg += st_g;
+        __syncthreads();
+    };
+
+    const int T_trips = T - T % NS;
+    const std::true_type yes{};
+    const std::false_type no{};
+    if (T_trips > 0) {                 // the first trip: k steps have stored in front of position k
+        auto first_step = [&](auto K) {
+            constexpr int k = decltype(K)::value;
+            run_step(std::integral_constant<int, L * D + S * k>{}, yes, k, ring[k], ring[(k + D) % NS]);
+        };
+        static_for(first_step, std::make_integer_sequence<int, NS>{});
+        // (inside the branch: no path of the built control flow enters the loop without the first trip)
+        for (int s0 = NS; s0 < T_trips; s0 += NS) {
+            auto trip_step = [&](auto K) {
+                constexpr int k = decltype(K)::value;
+                run_step(std::integral_constant<int, (L + S) * D>{}, yes, s0 + k, ring[k], ring[(k + D) % NS]);
+            };
+            static_for(trip_step, std::make_integer_sequence<int, NS>{});
+        }
+    }
+    // the last T mod (D + 1) steps: operands requested by the prologue or the loop
+    // (ONE copy of the tail for both cases: a second one, with the larger immediates a trip in front allows, made hipcc copy ring
+    // registers in front of their wait)
+    auto tail_step = [&](auto J) {
+        constexpr int j = decltype(J)::value;
+        run_step(std::integral_constant<int, L * (D - 1 - j) + S * j>{}, no, T_trips + j, ring[j], ring[j]);
+    };
+    static_while<0, D>(tail_step, T - T_trips);
+}
+
 // DIRECT = 1 (NW = 8, SEG = 0 only): the direct body above, its LDS the launch's dynamic request (BWD_DIRECT_LDS)
 template <int NW, int GRP, int SEG, int DIRECT = 0>
 __global__ __launch_bounds__(64 * NW) void gru_seq_bwd_kpart_kernel(BwdGroups G) {
@@ -1938,8 +2186,19 @@ bool use_staged_bwd() {
     return false;
 }
 
+// the plain one-sequence-per-CU forward recurrence runs the direct body (gru_fwd_direct_body); the tuning build keeps the
+// five-wave body selectable (MMDFN_GRU_FWD_STAGED=1) as its A/B partner and bit-for-bit test reference
+bool use_staged_fwd() {
+#ifdef MMDFN_TUNING
+    const char* e = getenv("MMDFN_GRU_FWD_STAGED");
+    if (e != nullptr) return e[0] == '1';
+#endif
+    return false;
+}
+
 static_assert(BWD_DIRECT_PART_B <= BWD_DIRECT_LDS && BWD_DIRECT_PART_B <= tnsb::LDS_B, "the partial sums sit in the launch's LDS");
 static_assert(2 * BWD_DIRECT_LDS > 160 * 1024, "one recurrence workgroup per CU");
+static_assert(2 * FWD_DIRECT_LDS > 160 * 1024, "one forward recurrence workgroup per CU");
 
 int pick_r(int ngroups, const int* rows) {
 #ifdef MMDFN_TUNING
@@ -1995,9 +2254,10 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
     hipStream_t s = (hipStream_t)stream;
     MmdfnRiders* rd = (MmdfnRiders*)riders;
     if (f.mfma && G.abl == 0) return mmdfn_launch_gru_fwd_mfma(f, ngroups, gi, w_hh, b_hh, y, gates, rows, T, rd, s);
-    // the 5-wave kernel runs one workgroup per CU (its fifth wave shares a SIMD with a recurrence wave at ~210 VGPRs each):
-    // it wins while every sequence gets a CU of its own in one round (cfg2: 160 workgroups); beyond that the 4-wave kernel,
-    // two workgroups per CU, needs fewer rounds (cfg3 / cfg4: +4-5 % step time with the 5-wave kernel, measured)
+    // the one-recurrence-per-CU kernel (gru_seq_fwd_io_kernel: the direct body on four waves, FWD_DIRECT_LDS keeps a CU to one
+    // workgroup; in the tuning library also the five-wave body it replaced) wins while every sequence gets a CU of its own in
+    // one round (cfg2: 160 workgroups); beyond that the blocked 4-wave kernel, two workgroups per CU, needs fewer rounds
+    // (cfg3 / cfg4: +4-5 % step time with one workgroup per CU, measured with the five-wave body)
     bool io_wave = (R == 1) && (2 * sl <= MMDFN_CUS);
 #ifdef MMDFN_TUNING
     if (const char* e = getenv("MMDFN_GRU_IO")) io_wave = io_wave && e[0] != '0';      // A/B aid
@@ -2015,14 +2275,31 @@ extern "C" int mmdfn_gru_seq_fwd(int ngroups, const float* const* gi, const floa
         // a staged dropout-flag draw rides on the CUs this launch leaves idle (gru_seq_fwd_io_flags_kernel)
         const kfb::FlagJob J = rd->flag_job;
         rd->flag_job_valid = false;
-        int64_t nr = (J.n8 + 319) / 320;
+#ifdef MMDFN_TUNING
+        if (use_staged_fwd()) {
+            int64_t nr5 = (J.n8 + 319) / 320;
+            if (nr5 > f.idle_cus) nr5 = f.idle_cus;
+            hipLaunchKernelGGL(gru_seq_fwd_io_flags_kernel<0>, dim3(2 * sl + (int)nr5), dim3(320), 0, s, G, J, sl);
+            MMDFN_CHECK_LAUNCH();
+            return 0;
+        }
+#endif
+        int64_t nr = (J.n8 + NT - 1) / NT;
         if (nr > f.idle_cus) nr = f.idle_cus;
-        hipLaunchKernelGGL(gru_seq_fwd_io_flags_kernel, dim3(2 * sl + (int)nr), dim3(320), 0, s, G, J, sl);
+        if (int e = mmdfn_allow_big_lds(gru_seq_fwd_io_flags_kernel<1>)) return e;
+        hipLaunchKernelGGL(gru_seq_fwd_io_flags_kernel<1>, dim3(2 * sl + (int)nr), dim3(NT), FWD_DIRECT_LDS, s, G, J, sl);
         MMDFN_CHECK_LAUNCH();
         return 0;
     }
     if (io_wave && scalar_fma) hipLaunchKernelGGL((gru_seq_fwd_io_kernel<1, 0, 0>), grid, dim3(320), 0, s, G);
-    else if (io_wave) hipLaunchKernelGGL((gru_seq_fwd_io_kernel<0, 0, 0>), grid, dim3(320), 0, s, G);
+#ifdef MMDFN_TUNING
+    else if (io_wave && use_staged_fwd()) hipLaunchKernelGGL((gru_seq_fwd_io_kernel<0, 0, 0>), grid, dim3(320), 0, s, G);
+#endif
+    else if (io_wave) {
+        // one sequence per CU: the direct body on four waves (gru_fwd_direct_body); its LDS request keeps a CU to one workgroup
+        if (int e = mmdfn_allow_big_lds(gru_seq_fwd_io_kernel<0, 0, 0, 1>)) return e;
+        hipLaunchKernelGGL((gru_seq_fwd_io_kernel<0, 0, 0, 1>), grid, dim3(NT), FWD_DIRECT_LDS, s, G);
+    }
     else if (R == 1) hipLaunchKernelGGL((gru_seq_fwd_kernel<1, 0>), grid, block, 0, s, G);
     else if (R == 2) hipLaunchKernelGGL((gru_seq_fwd_kernel<2, 0>), grid, block, 0, s, G);
     else hipLaunchKernelGGL((gru_seq_fwd_kernel<4, 0>), grid, block, 0, s, G);
