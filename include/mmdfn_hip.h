@@ -905,6 +905,42 @@ int mmdfn_pass_stats_accumulate(const float* logp, const int64_t* target, const 
                                 int64_t* meta, double* loss_sum, float* loss_hist, int64_t N, int C, int64_t ignore_index,
                                 int slots, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K14  Matching attention over a dialogue (ABI 23, additive; csrc/matching_attention.hip)
+ * ---------------------------------------------------------------------------
+ * MatchingAttention(att_type='general2') (model.py:66-76,84) for every query row at once.  X (Tq, B, D) queries, M (L, B, D)
+ * memory, mask (B, L) fp32 ("non-zero keeps"), all contiguous fp32 in device memory, rows 16-byte aligned:
+ *   z = <X[t,b,:], M[s,b,:]>,  e = (mask[b,s] != 0) exp(tanh z),  alpha[t,b,s] = e / sum_s e,  pool[t,b,:] = sum_s alpha M[s,b,:]
+ * Outputs: pool (Tq, B, D), alpha (Tq, B, L), aux (Tq, B, L) = tanh z (0 where the mask is), which the backward pass reads.
+ * A dialogue whose mask row is all zero: pool, alpha and every gradient of it are 0 (the reference: 0 / 0 = NaN).
+ * Backward for dpool (alpha is not differentiated through), ws: mmdfn_match_att_workspace(...) floats (it receives dz):
+ *   dP = <dpool[t,b,:], M[s,b,:]>,  r = sum_s alpha dP,  dz = alpha (dP - r)(1 - aux^2)
+ *   dX[t,b,:] = sum_s dz M[s,b,:]      dM[s,b,:] = sum_t dz X[t,b,:] + sum_t alpha dpool[t,b,:]
+ * Exact fp32 products (v_mfma_f32_16x16x4_f32), every reduction in a fixed order, no atomics: bit-reproducible.  One launch
+ * forward, two backward.  Served: D % 4 == 0, 4 <= D <= mmdfn_match_att_max_width(), 1 <= L <= mmdfn_match_att_max_len(),
+ * Tq >= 1, 1 <= B <= 65535; anything else (or a null operand) returns -1 before any launch (the workspace query too). */
+int mmdfn_match_att_max_width(void);
+int mmdfn_match_att_max_len(void);
+int64_t mmdfn_match_att_workspace(int Tq, int L, int B, int D);
+int mmdfn_match_att_fwd(const float* X, const float* M, const float* mask, float* pool, float* alpha, float* aux, int Tq,
+                        int L, int B, int D, void* stream);
+int mmdfn_match_att_bwd(const float* dpool, const float* X, const float* M, const float* mask, const float* alpha,
+                        const float* aux, float* dX, float* dM, float* ws, int Tq, int L, int B, int D, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * K15  MaskedNLLLoss (ABI 23, additive; csrc/nll_loss.hip beside K12; reference loss.py:38-58)
+ * ---------------------------------------------------------------------------
+ * loss = sum_i m_i w[t_i] (-pred[i, t_i]) / sum_i m_i w[t_i]   (weight NULL: w = 1).  pred (N, C) fp32, target N int64, mask N
+ * fp32 (the (B, L) utterance mask, rows in pred's order).  One workgroup of mmdfn_nll_loss_threads() threads, fixed-order
+ * reduction in float64, the denominator on the device.  coef[i] = -m_i w[t_i], scale_out[0] = 1 / denominator.  No row with a
+ * non-zero mask: loss 0, scale 0, zero gradients (the reference: NaN); a label outside [0, C) on a row that counts: NaN loss,
+ * NaN gradient row; rows whose mask is 0 do not read their label.  weight must hold C entries.
+ * Backward: dpred[i, c] = (c == t_i) coef[i] scale[0] dloss[0]; rows whose mask is 0 are written as exact zeros. */
+int mmdfn_masked_nll_fwd(const float* pred, const int64_t* target, const float* mask, const float* weight, float* loss,
+                         float* coef, float* scale_out, int64_t N, int C, void* stream);
+int mmdfn_masked_nll_bwd(const float* coef, const int64_t* target, const float* mask, const float* dloss, const float* scale,
+                         float* dpred, int64_t N, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ from .graph_conv import GraphConvolution, GCNII_lyc, GCNII  # noqa: F401
 from .mm_gcn import MM_GCN  # noqa: F401
 from .mm_gcn2 import MM_GCN2  # noqa: F401
 from .dialogue_model import DialogueGNNModel  # noqa: F401
-from .loss import FocalLoss, NLLLoss  # noqa: F401
+from .loss import FocalLoss, NLLLoss, MaskedNLLLoss  # noqa: F401
 from .fusion import MFN, MMGatedAttention  # noqa: F401
 from .multistream import MultiStreamGraphModel  # noqa: F401
+from .attention import MatchingAttention  # noqa: F401
+from .recurrent_models import GRUModel  # noqa: F401

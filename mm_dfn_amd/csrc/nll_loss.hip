@@ -113,3 +113,107 @@ extern "C" int mmdfn_nll_loss_bwd(const float* coef, const int64_t* target, cons
     MMDFN_CHECK_LAUNCH();
     return 0;
 }
+
+// K15: MaskedNLLLoss (reference loss.py:38-58), the objective of the recurrent baselines (run_train_erc.py:92-146):
+//   loss = sum_i m_i w[t_i] (-pred[i, t_i])  /  sum_i m_i w[t_i]          (w = 1 without a weight table; m: the 0 / 1 utterance mask)
+//   d loss / d pred[i, c] = (c == t_i) (-m_i w[t_i]) / sum_i m_i w[t_i]
+// The K12 launch shape: ONE workgroup, fixed row -> thread assignment, both sums in float64 through a fixed tree, the denominator
+// taken on the device.  Edge rules as K12: no row with a non-zero mask -> loss 0, scale 0 (the reference: 0 / 0 = NaN); a label
+// outside [0, C) on a row that counts -> NaN loss and a NaN gradient row.  Rows whose mask is 0 never read their label's column.
+namespace {
+
+__global__ __launch_bounds__(NLL_NT) void masked_nll_fwd_kernel(const float* __restrict__ pred, const int64_t* __restrict__ target,
+                                                                const float* __restrict__ mask, const float* __restrict__ weight,
+                                                                float* __restrict__ loss, float* __restrict__ coef,
+                                                                float* __restrict__ scale_out, int64_t N, int C) {
+    __shared__ double part[NLL_NT / 64];
+    __shared__ double wpart[NLL_NT / 64];
+    __shared__ int cpart[NLL_NT / 64];
+    double acc = 0.0, wsum = 0.0;
+    int cnt = 0;
+    for (int64_t i = threadIdx.x; i < N; i += NLL_NT) {
+        const float m = mask[i];
+        if (m == 0.f) {
+            coef[i] = 0.f;
+            continue;
+        }
+        int64_t t = target[i];
+        const bool bad = t < 0 || t >= C;
+        t = bad ? 0 : t;
+        const float lp = bad ? __builtin_nanf("") : pred[i * C + t];
+        float w = weight != nullptr ? weight[t] : 1.f;
+        if (bad) w = __builtin_nanf("");
+        const float mw = m * w;
+        coef[i] = -mw;
+        acc += (double)mw * (double)(-lp);
+        wsum += (double)mw;
+        ++cnt;
+    }
+    acc = wave_sum_f64(acc);
+    wsum = wave_sum_f64(wsum);
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    if ((threadIdx.x & 63) == 0) {
+        part[threadIdx.x >> 6] = acc;
+        wpart[threadIdx.x >> 6] = wsum;
+        cpart[threadIdx.x >> 6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0, ws = 0.0;
+        int n = 0;
+#pragma unroll
+        for (int w = 0; w < NLL_NT / 64; ++w) {
+            s += part[w];
+            ws += wpart[w];
+            n += cpart[w];
+        }
+        if (n == 0) {                       // every row masked: 0 with zero gradients
+            loss[0] = 0.f;
+            scale_out[0] = 0.f;
+        } else {                            // (all weights that count zero: 0 / 0 = NaN, as the reference)
+            loss[0] = (float)(s / ws);
+            scale_out[0] = (float)(1.0 / ws);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void masked_nll_bwd_kernel(const float* __restrict__ coef, const int64_t* __restrict__ target,
+                                                             const float* __restrict__ mask, const float* __restrict__ dloss,
+                                                             const float* __restrict__ scale, float* __restrict__ dpred,
+                                                             int64_t N, int C) {
+    const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (idx >= N * C) return;
+    const int64_t i = idx / C;
+    const int c = (int)(idx - i * C);
+    float v = 0.f;
+    if (mask[i] != 0.f) {
+        const int64_t t = target[i];
+        if (c == t || t < 0 || t >= C) v = coef[i] * scale[0] * dloss[0];     // bad label: coef is NaN
+    }
+    dpred[idx] = v;
+}
+
+}  // namespace
+
+extern "C" int mmdfn_masked_nll_fwd(const float* pred, const int64_t* target, const float* mask, const float* weight, float* loss,
+                                    float* coef, float* scale_out, int64_t N, int C, void* stream) {
+    if (N <= 0 || C <= 0 || pred == nullptr || target == nullptr || mask == nullptr || loss == nullptr || coef == nullptr ||
+        scale_out == nullptr)
+        return -1;
+    hipLaunchKernelGGL(masked_nll_fwd_kernel, dim3(1), dim3(NLL_NT), 0, (hipStream_t)stream, pred, target, mask, weight, loss,
+                       coef, scale_out, N, C);
+    MMDFN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mmdfn_masked_nll_bwd(const float* coef, const int64_t* target, const float* mask, const float* dloss,
+                                    const float* scale, float* dpred, int64_t N, int C, void* stream) {
+    if (N <= 0 || C <= 0 || coef == nullptr || target == nullptr || mask == nullptr || dloss == nullptr || scale == nullptr ||
+        dpred == nullptr)
+        return -1;
+    const int64_t total = N * C;
+    hipLaunchKernelGGL(masked_nll_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, coef,
+                       target, mask, dloss, scale, dpred, N, C);
+    MMDFN_CHECK_LAUNCH();
+    return 0;
+}

@@ -348,14 +348,18 @@ def bigru2(xs, grus, dropout=0.0, training=False, gi0=None, party=None):
     """xs[g]: (T, rows_g, 200) -> ys[g]: (T, rows_g, 200); grus[g]: the nn.GRU holding group g's weights.
     gi0[g] (optional): the first layer's gate pre-activations X W_ih^T + b_ih (T, rows_g, 600) computed by the caller
     (the party encoder projects the L*B utterances once and gathers the result instead of projecting the L*P*B
-    party rows); xs[g] is then ignored.
+    party rows); xs[g] is then ignored, and that group's nn.GRU may have any input_size (recurrent_models.GRUModel: 100 or
+    600 text features).
     party = (group index, rank (L, B, P) int32, PartyTable or None): run that group with the valid-length launches (layer 1:
     reverse direction truncated against the all-padding sequence when one is given; layer 2: forward direction truncated;
     silent rows skipped)."""
-    for gru in grus:
+    # a group whose first-layer pre-activations the caller supplies never has that layer contracted here: its input width is
+    # the caller's business (the recurrence kernels read gi only), and its weight_ih_l0 -- another shape -- stays out of ``wcat``
+    wide = [gi0 is not None and gi0[g] is not None and gru.input_size != 2 * H for g, gru in enumerate(grus)]
+    for g, gru in enumerate(grus):
         if gru.hidden_size != H or gru.num_layers != 2 or not gru.bidirectional or gru.batch_first:
             raise NotImplementedError("fused GRU path supports nn.GRU(*, 100, num_layers=2, bidirectional=True)")
-        if gru.input_size != 2 * H:
+        if gru.input_size != 2 * H and not wide[g]:
             # (both layers then share one (600, 200) stacked-weight shape: the copy fallback below relies on it)
             raise NotImplementedError("fused GRU path supports input_size == 2 * hidden_size (200) only, got %d" % gru.input_size)
     cur = list(xs)
@@ -365,15 +369,17 @@ def bigru2(xs, grus, dropout=0.0, training=False, gi0=None, party=None):
     wcat = bcat = None
     if torch.is_grad_enabled():
         pairs = [_layer_params(gru, layer)[0] for layer in range(2) for gru in grus]
-        wcat = [_stacked_view(wf, wr) for wf, wr in pairs]
+        skip = [layer == 0 and wide[g] for layer in range(2) for g in range(len(grus))]
+        wcat = [None if sk else _stacked_view(wf, wr) for sk, (wf, wr) in zip(skip, pairs)]
         # the stacked input biases [b_ih; b_ih_reverse] the same way (views only)
         bcat = [_stacked_view(bf, br) for bf, br in (_layer_params(gru, layer)[1] for layer in range(2) for gru in grus)]
-        if any(w is None for w in wcat):
-            halves = [w for pair in pairs for w in pair]
+        if any(w is None and not sk for w, sk in zip(wcat, skip)):
+            live = [i for i, sk in enumerate(skip) if not sk]
+            halves = [w for i in live for w in pairs[i]]
             with torch.no_grad():
                 wcat = torch.empty(len(pairs), 2 * halves[0].shape[0], halves[0].shape[1], dtype=halves[0].dtype,
                                    device=halves[0].device)
-                torch._foreach_copy_([wcat[i // 2, (i % 2) * halves[0].shape[0]:(i % 2 + 1) * halves[0].shape[0]]
+                torch._foreach_copy_([wcat[live[i // 2], (i % 2) * halves[0].shape[0]:(i % 2 + 1) * halves[0].shape[0]]
                                       for i in range(len(halves))], halves)
     pending = None                  # (keep flags, scale) of the dropout in front of the next layer
     for layer in range(2):

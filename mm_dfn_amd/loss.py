@@ -1,5 +1,6 @@
 """FocalLoss (reference loss.py:5-34): -(1-pt)^gamma * alpha_t * log(pt), pt detached; NLLLoss: the training script's other
-objective, torch.nn.NLLLoss(class weights) (run_train_erc.py:509)."""
+objective, torch.nn.NLLLoss(class weights) (run_train_erc.py:509); MaskedNLLLoss (loss.py:38-58): the objective of the reference's
+recurrent models (run_train_erc.py:92-146)."""
 import torch
 import torch.nn as nn
 
@@ -205,3 +206,73 @@ class NLLLoss(nn.Module):
             return _NLLLossHip.apply(input, target, weight, self.reduction == 'mean', self.ignore_index)
         import torch.nn.functional as F
         return F.nll_loss(input, target, weight, ignore_index=self.ignore_index, reduction=self.reduction)
+
+
+class _MaskedNLLLossHip(torch.autograd.Function):
+    """One launch each way (csrc/nll_loss.hip, K15): the forward writes the per-row coefficient -m_i w[t_i] and the reciprocal
+    of the denominator on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, weight):
+        from . import _hip
+        pred = pred.contiguous()
+        target = target.reshape(-1).contiguous()
+        mask = mask.reshape(-1).contiguous()
+        N, C = pred.shape
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        scale = torch.empty(1, dtype=torch.float32, device=pred.device)
+        coef = torch.empty(N, dtype=torch.float32, device=pred.device)
+        _hip.call("mmdfn_masked_nll_fwd", _hip.ptr(pred), _hip.ptr(target), _hip.ptr(mask), _hip.ptr(weight), _hip.ptr(loss),
+                  _hip.ptr(coef), _hip.ptr(scale), N, C, _hip.stream())
+        ctx.save_for_backward(coef, target, mask, scale)
+        ctx.C = C
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import _hip
+        coef, target, mask, scale = ctx.saved_tensors
+        N = coef.shape[0]
+        dpred = torch.empty(N, ctx.C, dtype=torch.float32, device=coef.device)
+        dl = dloss.contiguous().to(torch.float32)
+        _hip.call("mmdfn_masked_nll_bwd", _hip.ptr(coef), _hip.ptr(target), _hip.ptr(mask), _hip.ptr(dl), _hip.ptr(scale),
+                  _hip.ptr(dpred), N, ctx.C, _hip.stream())
+        return dpred, None, None, None
+
+
+class MaskedNLLLoss(nn.Module):
+    """The reference's ``MaskedNLLLoss(weight)`` (loss.py:38-58), the objective of its recurrent models: ``forward(pred, target,
+    mask)`` with pred (batch * seq_len, n_classes) log-probabilities, target (batch * seq_len) and mask (batch, seq_len) of 0 / 1:
+    ``sum_i m_i w[t_i] (-pred[i, t_i]) / sum_i m_i w[t_i]`` (w = 1 without a weight table).
+
+    Device tensors run one fused launch each way; both sums are reduced in a fixed order in float64 and the denominator stays
+    on the device.  Where it differs from the reference, as NLLLoss documents for its all-ignored case: with every row masked the
+    loss is 0 with zero gradients (the reference: 0 / 0 = NaN), and a label outside [0, C) on a row that counts gives a NaN loss
+    and a NaN gradient row (torch raises; a kernel cannot without a host synchronisation).  Gradient rows of masked positions
+    are exact zeros.  A weight table shorter than C raises IndexError.  Host tensors take the reference's torch formula
+    unchanged."""
+
+    def __init__(self, weight=None):
+        super().__init__()
+        if isinstance(weight, (list, tuple)):
+            weight = torch.tensor(weight, dtype=torch.float32)
+        self.weight = weight
+
+    def forward(self, pred, target, mask):
+        weight = self.weight
+        if weight is not None and (weight.device != pred.device or weight.dtype != pred.dtype):
+            weight = self.weight = weight.to(device=pred.device, dtype=pred.dtype)
+        if pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and target.dtype == torch.int64:
+            if weight is not None and weight.numel() < pred.shape[1]:
+                raise IndexError("MaskedNLLLoss: weight has %d entries for %d classes" % (weight.numel(), pred.shape[1]))
+            if mask.numel() != pred.shape[0] or target.numel() != pred.shape[0]:
+                raise ValueError("MaskedNLLLoss: pred has %d rows, target %d, mask %d" % (pred.shape[0], target.numel(), mask.numel()))
+            if weight is not None:
+                weight = weight.contiguous()
+            return _MaskedNLLLossHip.apply(pred, target, mask.to(torch.float32), weight)
+        # host tensors: loss.py:52-58 as written
+        mask_ = mask.view(-1, 1)
+        nll = torch.nn.functional.nll_loss(pred * mask_, target, weight, reduction='sum')
+        if weight is None:
+            return nll / torch.sum(mask)
+        return nll / torch.sum(weight[target] * mask_.squeeze())

@@ -55,6 +55,9 @@ from .ops_head import (  # noqa: F401
 from .ops_embed import (  # noqa: F401
     _GraphEmbeddings, graph_embeddings,
 )
+from .ops_attention import (  # noqa: F401
+    _MatchingAttention, matching_attention, matching_attention_supported,
+)
 from .ops_stats import (  # noqa: F401
     pass_stats_threads, pass_stats_max_classes, pass_stats_update, pass_stats_update_host, first_max,
 )

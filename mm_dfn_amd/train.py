@@ -736,6 +736,65 @@ def train_or_eval_graph_model(model, loss_f, dataloader, epoch=0, train_flag=Fal
     return all_each, all_acc, avg_loss, avg_accuracy, labels, preds, avg_fscore, [np.array(vids), losses]
 
 
+def train_or_eval_model(model, loss_f, dataloader, epoch=0, train_flag=False, optimizer=None, cuda_flag=False,
+                        target_names=None, tensorboard=False):
+    """The pass loop of the reference's recurrent models (run_train_erc.py:92-146: GRUModel and friends with MaskedNLLLoss):
+    same arguments, same 9-tuple ``(all_each, all_acc, avg_loss, avg_accuracy, labels, preds, masks, avg_fscore, [alphas,
+    alphas_f, alphas_b, vids])``.  Kept: batch tuple order (:106), the model call (:107), the dialogue-major flatten of the
+    log-probabilities (:108), metrics weighted by the utterance mask (:137-139), attention weights collected in evaluation
+    passes only (:125-128).  Changed for the device: the step runs eagerly through ``backward`` (the step's weight gradients
+    leave as one batch) and ``ops.join_weight_grads()`` in front of ``optimizer.step()``; predictions, labels, masks and
+    losses stay on the device and are copied to the host once at the end of the pass.  ``tensorboard`` is accepted and ignored
+    (the reference's writer is a global of its script)."""
+    losses, preds, labels, masks = [], [], [], []
+    alphas, alphas_f, alphas_b, vids = [], [], [], []
+    assert not train_flag or optimizer is not None
+    model.train() if train_flag else model.eval()
+    for data in dataloader:
+        if train_flag:
+            optimizer.zero_grad()
+        textf, visuf, acouf, qmask, umask, label = [d.cuda() for d in data[:-1]] if cuda_flag else data[:-1]
+        log_prob, alpha, alpha_f, alpha_b, _ = model(textf, qmask, umask)
+        lp_ = log_prob.transpose(0, 1).contiguous().view(-1, log_prob.size()[2])
+        labels_ = label.view(-1)
+        loss = loss_f(lp_, labels_, umask)
+        preds.append(torch.argmax(lp_.detach(), 1))
+        labels.append(labels_)
+        masks.append(umask.reshape(-1))
+        losses.append(loss.detach())
+        if train_flag:
+            backward(loss)
+            ops.join_weight_grads()       # weight gradients still queued are written to .grad here
+            optimizer.step()
+        else:
+            alphas += alpha
+            alphas_f += alpha_f
+            alphas_b += alpha_b
+            vids += data[-1]
+    if not preds:
+        return [], [], float('nan'), float('nan'), [], [], [], float('nan'), []
+    # the pass's one round of device -> host copies
+    counts = torch.stack([m.to(torch.float64).sum() for m in masks]).cpu().numpy()       # (run_train_erc.py:117)
+    preds = torch.cat(preds).cpu().numpy()
+    labels = torch.cat(labels).cpu().numpy()
+    masks = torch.cat(masks).cpu().numpy()
+    losses = torch.stack(losses).to(torch.float64).cpu().numpy()
+    from sklearn import metrics
+    from sklearn.metrics import accuracy_score, f1_score
+    avg_loss = round(float(np.sum(losses * counts)) / float(np.sum(masks)), 4)
+    avg_accuracy = round(accuracy_score(labels, preds, sample_weight=masks) * 100, 2)
+    avg_fscore = round(f1_score(labels, preds, sample_weight=masks, average='weighted') * 100, 2)
+    all_each, all_acc = "", ["ACC"]
+    if target_names is not None:
+        all_each = metrics.classification_report(labels, preds, target_names=target_names, digits=4,
+                                                 labels=list(range(len(target_names))), zero_division=0)
+        for i, name in enumerate(target_names):
+            sel = labels == i
+            acc = accuracy_score(labels[sel], preds[sel]) if sel.any() else float('nan')
+            all_acc.append("{}: {:.4f}".format(name, acc))
+    return all_each, all_acc, avg_loss, avg_accuracy, labels, preds, masks, avg_fscore, [alphas, alphas_f, alphas_b, vids]
+
+
 def fit(model, loss_f, optimizer, train_loader, valid_loader, test_loader, n_epochs, patience=10, valid_rate=0.1,
         cuda_flag=False, modals=None, target_names=None, run_pass=None, log=print, step_hook=None, graph_cache=None,
         device_metrics=False, reduce_group=None):
