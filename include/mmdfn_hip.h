@@ -942,6 +942,33 @@ int mmdfn_masked_nll_fwd(const float* pred, const int64_t* target, const float* 
 int mmdfn_masked_nll_bwd(const float* coef, const int64_t* target, const float* mask, const float* dloss, const float* scale,
                          float* dpred, int64_t N, int C, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K16  fused LSTM recurrence (ABI 23, additive; csrc/lstm_seq.hip; the time loop inside the reference's
+ * LSTMModel.lstm = nn.LSTM(D_m, 100, num_layers=2, bidirectional=True), model.py:320-356)
+ * ---------------------------------------------------------------------------
+ * One layer, both directions, one launch each way; one persistent workgroup per (sequence, direction).  Contiguous fp32 in
+ * device memory; w_hh / b_hh are HOST arrays of two device pointers (forward, reverse):
+ *   gi      : (T, rows, 8H)  X W_ih^T + b_ih, direction-major: forward [i f g o], then reverse [i f g o] (torch gate order)
+ *   w_hh[d] : (4H, H), b_hh[d] : (4H)  exactly as nn.LSTM stores weight_hh_l*[_reverse] / bias_hh_l*[_reverse]
+ *   y       : (T, rows, 2H) out, forward and reverse outputs side by side; direction 1 runs t = T-1 .. 0
+ *   state   : (T, rows, 2, 5, H) out: i, f, g, o, c_t -- what the backward pass needs and nothing more (tanh(c_t) is
+ *             recomputed; c_{t-1} is the previous (forward) / next (reverse) row block's c)
+ *   dgate   : (T, rows, 8H) out, the gradient of the four pre-activations in gi's layout.  It is the gradient of both the
+ *             input-side and the hidden-side pre-activations (so db_hh = db_ih); weight gradients are the caller's contractions.
+ * Both directions start from h = c = 0; (h_n, c_n) is not an output.
+ *   forward step :  a = W_hh h + b_hh + gi;  i, f, o = sig(.);  g = tanh(.);  c' = f c + i g;  h' = o tanh(c')
+ *   backward step (per direction, in the reverse of its processing order):
+ *     tc = tanh(c');  do = dh tc o (1-o);  dc = dc_carry + dh o (1 - tc^2);  di = dc g i (1-i);  df = dc c_prev f (1-f);
+ *     dg = dc i (1 - g^2);  dc_carry = dc f;  dh_prev = dy_prev + dgate W_hh
+ * The backward pass reads dy, state and w_hh (y is part of the signature for the caller's dW_hh contraction; it must be valid).
+ * Both entry points return -1 before any HIP call for H != 100, rows <= 0, T <= 0 or any null pointer (the two entries of
+ * w_hh / b_hh included).  mmdfn_lstm_seq_block_steps(): timesteps per staged block of operands (launch edges for tests). */
+int mmdfn_lstm_seq_block_steps(void);
+int mmdfn_lstm_seq_fwd(const float* gi, const float* const* w_hh, const float* const* b_hh, float* y, float* state,
+                       int rows, int T, int H, void* stream);
+int mmdfn_lstm_seq_bwd(const float* dy, const float* y, const float* state, const float* const* w_hh, float* dgate,
+                       int rows, int T, int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
