@@ -969,6 +969,50 @@ int mmdfn_lstm_seq_fwd(const float* gi, const float* const* w_hh, const float* c
 int mmdfn_lstm_seq_bwd(const float* dy, const float* y, const float* state, const float* const* w_hh, float* dgate,
                        int rows, int T, int H, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K17  fused DialogueRNN recurrence (ABI 23, additive; csrc/dialogue_rnn.hip; the time loop of the reference's
+ * DialogueRNN / DialogueRNNCell, model.py:168-278, both directions of DialogRNNModel, model.py:359-417, in one launch)
+ * ---------------------------------------------------------------------------
+ * Grid (ceil(B / R), ndir), ndir = 1 (a DialogueRNN on its own: direction 0 only; the arrays below then hold one direction and
+ * the buffers keep their leading 2) or 2, R = mmdfn_drnn_chains_per_group(): a workgroup owns R chains of one direction for the whole sequence
+ * and streams the state-side weights once per step for all of them.  Direction 1 runs each dialogue reversed within its own
+ * length (t = len-1 .. 0) and stops there; direction 0 runs all T steps.  "Chain-step order" below: row s of a chain is its
+ * s-th processed step (time s for direction 0, time len-1-s for direction 1).  Contiguous fp32 / int32 device memory; pu, img,
+ * keep_*, w, dpu are HOST arrays of device pointers, [direction] (w: [direction][6]).
+ *   pu[d]    : (T, B, npu) in TIME order, npu = 900 ('simple', att = 0) or 1050 ('general', att = 1):
+ *              [U W_ih_g[:, :D_m]^T + b_ih_g (450) | U W_ih_p[:, :D_m]^T + b_ih_p (450) | U W_att^T (150)]
+ *   img[d]   : mmdfn_drnn_image_floats() floats, the forward weight image, k-major (transposed) matrices then vectors:
+ *              W_ih_g[:, D_m:]^T (150,450) | W_hh_g^T (150,450) | W_ih_p[:, D_m:]^T (150,450) | W_hh_p^T (150,450) |
+ *              W_ih_e^T (150,300) | W_hh_e^T (100,300) | b_hh_g (450) | b_hh_p (450) | b_ih_e (300) | b_hh_e (300) |
+ *              SimpleAttention.scalar.weight (150) + 2 zeros
+ *   w[d][i]  : backward: the same six matrices as nn.GRUCell stores them (gate row j, column k), row strides ld[i]
+ *              (W_ih_g[:, D_m:] is the pointer weight_ih + D_m with ld = D_m + 150)
+ *   speaker  : (T, B) int32 argmax of qmask (clamped to [0, P));  upd : (T, B) qmask at the speaker (0 or 1);  lengths : (B)
+ *   keep_*   : NULL (no dropout), or per direction NULL / 0-1 flags in chain-step order: g, q (T, B, 150), e (T, B, 100);
+ *              kept values are multiplied by keep_scale
+ *   e_out    : (2, T, B, 100) in TIME order;  alpha : (2, T, B, T) chain-step order, row s holds alpha_sj for j < s
+ *   state    : (2, 17, T, B, 152) chain-step order, planes r z n hn of the g cell, g (dropped, carried), r z n hn of the p
+ *              cell, q_{s-1}[speaker], q_s[speaker], c, r z n hn of the e cell, e (dropped, carried); columns past the width
+ *              (150 / 100) are padding
+ *   dgate    : (2, 6, T, B, 452) chain-step order: dgi_g dgh_g dgi_p dgh_p dgi_e dgh_e (gradients of the input-side and the
+ *              hidden-side pre-activations: they differ in the n block);  dpu[d] : (T, B, npu) TIME order
+ *   dghist   : (2, T, B, 152) workspace (the history gradient);  dw_part : (2, B, 152) per-chain dw of 'simple' (att = 0)
+ * e_out, alpha, state, dgate, dpu, dghist must be ZERO on entry: the kernels write only the steps below a chain's length and
+ * the columns below a plane's width.  Both entry points return -1 before any HIP call for a null pointer or an unserved size
+ * (served: Dg = Dp = 150, De = 100, 1 <= P <= 16, 1 <= T <= 1008, B >= 1, npu as above, att 0 / 1, ndir 1 / 2, ld[i] >= the
+ * width). */
+int mmdfn_drnn_chains_per_group(void);
+int64_t mmdfn_drnn_image_floats(void);
+int mmdfn_drnn_seq_fwd(const float* const* pu, const float* const* img, const int32_t* speaker, const float* upd,
+                       const int32_t* lengths, const float* const* keep_g, const float* const* keep_q,
+                       const float* const* keep_e, float keep_scale, float* e_out, float* alpha, float* state, int B, int T,
+                       int P, int Dg, int Dp, int De, int npu, int att, int ndir, void* stream);
+int mmdfn_drnn_seq_bwd(const float* de_out, const float* const* pu, const float* const* img, const float* const* w,
+                       const int32_t* ld, const int32_t* speaker, const float* upd, const int32_t* lengths,
+                       const float* const* keep_g, const float* const* keep_q, const float* const* keep_e, float keep_scale,
+                       const float* alpha, const float* state, float* dgate, float* const* dpu, float* dghist, float* dw_part,
+                       int B, int T, int P, int Dg, int Dp, int De, int npu, int att, int ndir, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

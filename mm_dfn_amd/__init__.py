@@ -14,4 +14,5 @@ from .loss import FocalLoss, NLLLoss, MaskedNLLLoss  # noqa: F401
 from .fusion import MFN, MMGatedAttention  # noqa: F401
 from .multistream import MultiStreamGraphModel  # noqa: F401
 from .attention import MatchingAttention  # noqa: F401
-from .recurrent_models import GRUModel, LSTMModel  # noqa: F401
+from .dialogue_rnn import DialogueRNN  # noqa: F401
+from .recurrent_models import GRUModel, LSTMModel, DialogRNNModel  # noqa: F401

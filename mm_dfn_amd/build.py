@@ -28,7 +28,9 @@ NO_SPILL = {"gru.hip": ("gru_seq_bwd_kpart_kernelILi8ELi4ELi0ELi1E", "gru_seq_bw
                         "gru_seq_fwd_io_kernelILi0ELi0ELi0ELi1E", "gru_seq_fwd_io_flags_kernelILi1E"),
             # (lstm_seq.hip has no hand-counted waits: its budget is W_hh in registers -- 208 / 200 weights per lane -- and a
             # spill would put scratch traffic on every timestep of the serial chain)
-            "lstm_seq.hip": ("lstm_seq_fwd_kernel", "lstm_seq_bwd_kernel")}
+            "lstm_seq.hip": ("lstm_seq_fwd_kernel", "lstm_seq_bwd_kernel"),
+            # (dialogue_rnn.hip: R accumulators per contraction and lane; scratch traffic would sit on the serial chain)
+            "dialogue_rnn.hip": ("drnn_seq_fwd_kernel", "drnn_seq_bwd_kernel")}
 
 
 def sources():
