@@ -1013,6 +1013,46 @@ int mmdfn_drnn_seq_bwd(const float* de_out, const float* const* pu, const float*
                        const float* alpha, const float* state, float* dgate, float* const* dpu, float* dghist, float* dw_part,
                        int B, int T, int P, int Dg, int Dp, int De, int npu, int att, int ndir, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K18  fused embedding -> Conv1d -> ReLU -> max over time (ABI 23, additive; csrc/cnn_features.hip; the pooled
+ * block of the reference's CNNFeatureExtractor, model.py:1410-1443)
+ * ---------------------------------------------------------------------------
+ * Contiguous device memory; conv_w / conv_b / d_w / d_b are HOST arrays of n_k device pointers, ksizes a HOST array of n_k sizes:
+ *   tokens     : (rows, W) int64 token ids.  The caller validates them; the kernels clamp an id into [0, V) before every read.
+ *   table      : (V, D) fp32, the embedding table
+ *   conv_w[i]  : (F, D, K_i) fp32, conv_b[i] : (F), exactly as nn.Conv1d stores them
+ *   row_mask   : (rows) fp32; a row whose mask is 0 is skipped: pooled 0, argmax -1
+ *   planes     : workspace of mmdfn_cnn_planes_bytes(D, F, n_k, ksizes) bytes: the bf16 piece fragments of every tap, cut by
+ *                the forward launch itself (nothing to keep fresh between steps)
+ *   pooled     : (rows, n_k F) out, column i F + f = max_t relu(b_i[f] + sum_{k, c} W_i[f, c, k] E[tok[r, t + k], c]), 0 <= t <= W - K_i
+ *   argmax     : (rows, n_k F) int32 out, the LOWEST t attaining the maximum; -1 where the maximum is <= 0 (no gradient)
+ * mmdfn_cnn_pool_bwd writes (does not accumulate) d_w[i] (F, D, K_i) and d_b[i] (F) from d_pooled (rows, n_k F) and the saved
+ * argmax, rows summed in ascending order.  The table gradient is a family of its own, launched only for a trainable table:
+ *   mmdfn_cnn_table_entries = rows n_k F max K, the number of (row, column, tap) entries;
+ *   mmdfn_cnn_table_keys writes keys (entries) int32: the token entry (r, column, k) touched, V for a dead one (k >= K_i or
+ *     argmax -1);  the caller sorts them STABLY (sorted_keys, order = the int64 permutation);
+ *   mmdfn_cnn_table_bwd writes all of d_table (V, D): token v's entries summed in sorted order, zeros for a token without any
+ *     (bounds: a workspace of V + 1 int64, the tokens' segments in the sorted keys, written by a launch of its own).
+ * No float atomics anywhere: the same inputs give the same bits.  Every entry point returns -1 before any HIP call for a null
+ * pointer or an unserved size (served: D % 4 == 0 in 4..304, F in 1..64, n_k in 1..4, K_i in 1..8, max K <= W <= 512,
+ * rows >= 1, V >= 1); the size queries return -1 likewise.  mmdfn_cnn_tile_words(): window starts per staged tile;
+ * mmdfn_cnn_rows_per_group(): utterance rows per workgroup (launch edges for tests). */
+int mmdfn_cnn_tile_words(void);
+int mmdfn_cnn_rows_per_group(void);
+int64_t mmdfn_cnn_planes_bytes(int D, int F, int n_k, const int32_t* ksizes);
+int mmdfn_cnn_pool_fwd(const int64_t* tokens, const float* table, const float* const* conv_w, const float* const* conv_b,
+                       const float* row_mask, void* planes, float* pooled, int32_t* argmax, int64_t rows, int W, int V, int D,
+                       int F, int n_k, const int32_t* ksizes, void* stream);
+int mmdfn_cnn_pool_bwd(const float* d_pooled, const int32_t* argmax, const int64_t* tokens, const float* table,
+                       float* const* d_w, float* const* d_b, int64_t rows, int W, int V, int D, int F, int n_k,
+                       const int32_t* ksizes, void* stream);
+int64_t mmdfn_cnn_table_entries(int64_t rows, int F, int n_k, const int32_t* ksizes);
+int mmdfn_cnn_table_keys(const int32_t* argmax, const int64_t* tokens, int32_t* keys, int64_t rows, int W, int V, int F,
+                         int n_k, const int32_t* ksizes, void* stream);
+int mmdfn_cnn_table_bwd(const float* d_pooled, const int32_t* sorted_keys, const int64_t* order, const float* const* conv_w,
+                        int64_t* bounds, float* d_table, int64_t rows, int V, int D, int F, int n_k, const int32_t* ksizes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,3 +16,4 @@ from .multistream import MultiStreamGraphModel  # noqa: F401
 from .attention import MatchingAttention  # noqa: F401
 from .dialogue_rnn import DialogueRNN  # noqa: F401
 from .recurrent_models import GRUModel, LSTMModel, DialogRNNModel  # noqa: F401
+from .cnn_features import CNNFeatureExtractor  # noqa: F401

@@ -30,7 +30,10 @@ NO_SPILL = {"gru.hip": ("gru_seq_bwd_kpart_kernelILi8ELi4ELi0ELi1E", "gru_seq_bw
             # spill would put scratch traffic on every timestep of the serial chain)
             "lstm_seq.hip": ("lstm_seq_fwd_kernel", "lstm_seq_bwd_kernel"),
             # (dialogue_rnn.hip: R accumulators per contraction and lane; scratch traffic would sit on the serial chain)
-            "dialogue_rnn.hip": ("drnn_seq_fwd_kernel", "drnn_seq_bwd_kernel")}
+            "dialogue_rnn.hip": ("drnn_seq_fwd_kernel", "drnn_seq_bwd_kernel"),
+            # (cnn_features.hip: two accumulators and six operand fragments per lane in the tap loop; scratch traffic would sit
+            # between the fragment reads and the MFMAs of every k-step)
+            "cnn_features.hip": ("cnn_pool_fwd_kernel",)}
 
 
 def sources():

@@ -100,6 +100,39 @@ class MELDDataset(_DialogueDataset):
                 vid)
 
 
+class DailyDialogueDataset(Dataset):
+    """dataloader.py:71-101: the tokenised corpus.  The pickle is a 7-tuple (Speakers, Features, ActLabels, EmotionLabels,
+    trainId, testId, validId); Features[conv] is (utterances, words) token ids, Speakers[conv] a sequence of '0' / '1'.  An item
+    is (tokens (n, words) float, qmask (n, 2), umask (n), label (n) long, conv); a batch is [tokens (L, B, words), qmask (L, B, 2),
+    umask (B, L), label (B, L), ids] -- the ids travel as floats, as in the reference (CNNFeatureExtractor calls .long())."""
+
+    def __init__(self, split, path):
+        with open(path, 'rb') as f:
+            (self.Speakers, self.Features, self.ActLabels, self.EmotionLabels, self.trainId, self.testId,
+             self.validId) = pickle.load(f)
+        if split not in ("train", "test", "valid"):
+            raise ValueError("DailyDialogueDataset: split must be 'train', 'test' or 'valid', got %r" % (split,))
+        self.keys = [x for x in {"train": self.trainId, "test": self.testId, "valid": self.validId}[split]]
+        self.len = len(self.keys)
+
+    def __getitem__(self, index):
+        conv = self.keys[index]
+        return (torch.FloatTensor(np.asarray(self.Features[conv], dtype=np.float32)),
+                torch.FloatTensor([[1, 0] if x == '0' else [0, 1] for x in self.Speakers[conv]]),
+                torch.FloatTensor([1] * len(self.EmotionLabels[conv])),
+                torch.LongTensor(self.EmotionLabels[conv]),
+                conv)
+
+    def __len__(self):
+        return self.len
+
+    def collate_fn(self, data):
+        """dataloader.py:99-101: columns 0-1 padded time-major, 2-3 batch-major, 4 a list."""
+        cols = list(zip(*data))
+        return [pad_sequence(list(c)) if i < 2 else pad_sequence(list(c), True) if i < 4 else list(c)
+                for i, c in enumerate(cols)]
+
+
 def get_train_valid_sampler(trainset, valid=0.1):
     """run_train_erc.py:29-33: the first ``valid`` fraction of the train split is the validation set."""
     size = len(trainset)
@@ -345,4 +378,26 @@ def write_synthetic_pickle(path, dataset="IEMOCAP", n_train=24, n_test=8, max_le
         blob = blob + (None,)
     with open(path, "wb") as f:
         pickle.dump(blob, f)
+    return path
+
+
+def write_synthetic_dailydialog_pickle(path, lengths=(3, 1, 2), n_words=12, vocab_size=60, n_classes=7, n_test=1, n_valid=1,
+                                       seed=0):
+    """A token file with DailyDialogueDataset's 7-tuple layout, RandomState-seeded: one train dialogue per entry of ``lengths``
+    (utterances), then ``n_test`` + ``n_valid`` more of the first length.  Ids are in [1, vocab_size); 0 pads an utterance's tail."""
+    rs = np.random.RandomState(seed)
+    lens = list(lengths) + [lengths[0]] * (n_test + n_valid)
+    ids = ["conv%03d" % i for i in range(len(lens))]
+    spk, feat, act, emo = {}, {}, {}, {}
+    for cid, n in zip(ids, lens):
+        tok = rs.randint(1, vocab_size, size=(n, n_words))
+        for u in range(n):
+            tok[u, int(rs.randint(1, n_words + 1)):] = 0
+        feat[cid] = tok.tolist()
+        spk[cid] = [str(int(s)) for s in rs.randint(0, 2, size=n)]
+        act[cid] = [int(x) for x in rs.randint(0, 4, size=n)]
+        emo[cid] = [int(x) for x in rs.randint(0, n_classes, size=n)]
+    nt = len(lengths)
+    with open(path, "wb") as f:
+        pickle.dump((spk, feat, act, emo, ids[:nt], ids[nt:nt + n_test], ids[nt + n_test:]), f)
     return path
