@@ -127,20 +127,21 @@ def cut(x):
     return pieces
 
 
-def emulate(X, W, drop=None, swap_k=None):
-    """X W^T as the piece kernels form it: truncating cut, the six products in the order of six(), each product's 16-wide k-step
-    added to a float32 accumulator (the exact sum of the step, rounded once).  ``drop``: a name of PRODUCTS to leave out;
-    ``swap_k`` = (k1, k2): exchange these two k indices of W only (a fragment-layout fault)."""
+def emulate(X, W, drop=None, swap_k=None, step=16):
+    """X W^T as the piece kernels form it: truncating cut, the six products in the order of six(), each product's ``step``-wide
+    k-step (16; 32 in the weight-gradient kernels) added to a float32 accumulator (the exact sum of the step, rounded once).
+    ``drop``: a name of PRODUCTS to leave out; ``swap_k`` = (k1, k2): exchange these two k indices of W only (a fragment-layout
+    fault)."""
     X, W = np.asarray(X, np.float32), np.array(W, np.float32)
     if swap_k is not None:
         k1, k2 = swap_k
         W[:, [k1, k2]] = W[:, [k2, k1]]
     a, b = cut(X), cut(W)
     acc = np.zeros((X.shape[0], W.shape[0]), np.float32)
-    for k0 in range(0, X.shape[1], 16):
+    for k0 in range(0, X.shape[1], step):
         for name, (i, j) in PRODUCTS.items():
             if name == drop:
                 continue
-            step = a[i][:, k0:k0 + 16].astype(np.float64) @ b[j][:, k0:k0 + 16].astype(np.float64).T
-            acc = (acc.astype(np.float64) + step).astype(np.float32)
+            term = a[i][:, k0:k0 + step].astype(np.float64) @ b[j][:, k0:k0 + step].astype(np.float64).T
+            acc = (acc.astype(np.float64) + term).astype(np.float32)
     return acc
